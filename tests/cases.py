@@ -7,6 +7,18 @@ def int_matrix(seed, n_in, n_out, lo, hi):
     return np.random.default_rng(seed).integers(lo, hi, (n_in, n_out)).astype(np.float32)
 
 
+def array_digest(*arrays):
+    """sha256 over the shapes and float64 values of arrays: equal for arrays that np.array_equal calls equal (-0.0 counts as 0.0)"""
+    import hashlib
+
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.asarray(a, np.float64) + 0.0
+        h.update(repr(a.shape).encode())
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
 def reference_style_kernel(seed, n, bits):
     """The generator of the reference's tests/test_cmvm.py:17-20, seeded."""
     r = np.random.default_rng(seed)

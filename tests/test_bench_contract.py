@@ -136,7 +136,7 @@ def test_bench_runs_end_to_end_at_eight_ranks_on_the_emulated_device():
     if not emu.exists():
         pytest.skip('tests/emu/libda4ml_emu.so is not built')
     env = dict(os.environ, DA4ML_HIP_LIB=str(emu), HIPEMU_DEVICES='8')
-    r = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--gpus', '8', '--steps', '1', '--warmup', '0', '--cpu-seconds', '0', '--workload', 't0_plumbing_12x10_batch3_single_chain'],
+    r = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--full', '--gpus', '8', '--steps', '1', '--warmup', '0', '--cpu-seconds', '0', '--workload', 't0_plumbing_12x10_batch3_single_chain'],
                        capture_output=True, text=True, timeout=900, env=env)  # fmt: skip
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
@@ -145,6 +145,49 @@ def test_bench_runs_end_to_end_at_eight_ranks_on_the_emulated_device():
     v = line['check']['verify']
     assert v['all_ok'] is True and v['kernel_reproduced'] == v['of'] == 3
     assert line['engine']['picks_known_a_step_ahead'] > 0.5
+
+
+def test_plain_bench_run_dumps_the_last_step_on_the_emulated_device(tmp_path):
+    """A plain run (no --full) puts no roofline, CPU baseline or verification on its line, and --dump-outputs writes what the last timed
+    step computed: the dumped stages of the sampled results replay to the benchmark's own matrices, cost / adders agree with the line's
+    seed0, and a second run with the same arguments writes the same arrays."""
+    import os
+
+    import numpy as np
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    emu = ROOT / 'tests' / 'emu' / 'libda4ml_emu.so'
+    if not emu.exists():
+        pytest.skip('tests/emu/libda4ml_emu.so is not built')
+    env = dict(os.environ, DA4ML_HIP_LIB=str(emu), HIPEMU_DEVICES='1')
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f'run{run}'
+        r = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--steps', '2', '--warmup', '1', '--workload', 't0_plumbing_12x10_batch3_single_chain',
+                            '--dump-outputs', str(out)], capture_output=True, text=True, timeout=900, env=env)  # fmt: skip
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+        assert line['steps'] == 2 and line['ms_per_step'] > 0 and line['unit'] == 'solves/s'
+        assert not {'roofline', 'cpu_baseline'} & set(line) and 'verify' not in line['check']
+        dumps.append({p.stem: np.load(p) for p in sorted(out.glob('*.npy'))})
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    d = dumps[0]
+    assert all(a.dtype == np.float64 for a in d.values()) and sum(a.nbytes for a in d.values()) <= bench.DUMP_LIMIT
+    assert d['cost'][0] == line['check']['seed0']['cost'] and d['adders'][0] == line['check']['seed0']['adders']
+    kernels = bench.make_batch(12, 10, 3, first_seed=0)
+    for i, k in enumerate(kernels):  # a batch of 3: every result is in the sample
+        mat, s = None, 0
+        while f'result{i:03d}_stage{s}_ops' in d:
+            ops, outs = d[f'result{i:03d}_stage{s}_ops'], d[f'result{i:03d}_stage{s}_outputs'].astype(np.int64)
+            inp = d[f'result{i:03d}_stage{s}_inputs'].astype(np.int64)
+            stage = bench.replay_stage(len(inp), inp, outs[:, 0], outs[:, 1], outs[:, 2], ops[:, :4].astype(np.int64))
+            mat = stage if mat is None else mat @ stage
+            assert ops.shape[1] == 9
+            s += 1
+        assert s >= 1 and np.array_equal(mat, k.astype(np.float64)), i
+        assert d['cost'][i] == sum(d[f'result{i:03d}_stage{t}_ops'][:, 8].sum() for t in range(s))
 
 
 @pytest.mark.parametrize('workload,world', [('t0_plumbing_12x10_column_sharded', 8), ('t0_plumbing_12x10_column_sharded', 1), ('t0_plumbing_12x10_candidate_sharded', 8)])
@@ -159,7 +202,7 @@ def test_bench_c4_layouts_on_the_emulated_device(workload, world):
     if not emu.exists():
         pytest.skip('tests/emu/libda4ml_emu.so is not built')
     env = dict(os.environ, DA4ML_HIP_LIB=str(emu), HIPEMU_DEVICES='8', DA4ML_HIP_UPD_BLOCKS='8')
-    r = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--gpus', str(world), '--steps', '1', '--warmup', '1', '--workload', workload], capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, str(ROOT / 'bench.py'), '--full', '--gpus', str(world), '--steps', '1', '--warmup', '1', '--workload', workload], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
     assert line['n_gpus'] == world and line['scaling'] == 'strong' and line['unit'] == 'solves/s' and line['config']['workload'] == workload

@@ -9,7 +9,7 @@ OUT=gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 # 1. the driver's contract line (incl. the all-core CPU baseline and the replay of all 64 results)
-[ -n "${PMC_ONLY:-}" ] || { [ -n "${SKIP_BENCH:-}" ] && [ -s $OUT/bench.json ]; } || python bench.py --steps 2 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err   # SKIP_BENCH=1: keep the line of an earlier call
+[ -n "${PMC_ONLY:-}" ] || { [ -n "${SKIP_BENCH:-}" ] && [ -s $OUT/bench.json ]; } || python bench.py --full --steps 2 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err   # SKIP_BENCH=1: keep the line of an earlier call
 # 2. kernel trace + stats of the same workload (one step, no CPU leg, no verification)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o c3 -- python bench.py --steps 1 --warmup 0 --cpu-seconds 0 --no-verify > $OUT/trace.log 2>&1
 cp $OUT/trace/c3_kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/null
@@ -31,8 +31,8 @@ for SET in "${SETS[@]}"; do
 done
 [ -n "${QUICK:-}${PMC_ONLY:-}" ] && { ls -la $OUT; exit 0; }
 # 4. the other workloads: 64x64 batch, end-to-end model compile (C5), column-sharded chain (one GPU: phases forced, exchanges no-ops)
-timeout 300 python bench.py --workload c2_64x64_int8_batch64_single_chain --steps 5 --warmup 1 --cpu-seconds 0 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
-timeout 600 python bench.py --workload c5_model_batch --steps 3 --warmup 1 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+timeout 300 python bench.py --full --workload c2_64x64_int8_batch64_single_chain --steps 5 --warmup 1 --cpu-seconds 0 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+timeout 600 python bench.py --full --workload c5_model_batch --steps 3 --warmup 1 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
 timeout 600 python tools/shard_bench.py 256 > $OUT/column_sharded.txt 2>&1
 # 5. DAIS device executor (k_dais_run): throughput line + kernel stats
 if [ "${DAIS:-1}" != "0" ]; then

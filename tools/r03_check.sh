@@ -1,11 +1,12 @@
 #!/bin/bash
 # GPU parity suite + one short bench line (no CPU leg) + timing of both engines: the quick check after a change
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/check; rm -f gpurun_out/check/*
-timeout 1500 python -m pytest tests -m gpu -x -q "$@" 2>&1 | tail -6 | tee gpurun_out/check/parity.log
-timeout 600 python bench.py --steps 3 --warmup 1 --cpu-seconds 0 > gpurun_out/check/bench.json 2> gpurun_out/check/bench.err; tail -3 gpurun_out/check/bench.err
-python - <<'PY'
-import json
-d = json.loads(open('gpurun_out/check/bench.json').read().strip().splitlines()[-1])
+# outputs go to $O (a new temporary directory when it is not set)
+cd "$(dirname "$0")/.."; O=${O:-$(mktemp -d)}; mkdir -p "$O"; echo "outputs: $O"
+timeout 1500 python -m pytest tests -m gpu -x -q "$@" 2>&1 | tail -6 | tee "$O/parity.log"
+timeout 600 python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 > "$O/bench.json" 2> "$O/bench.err"; tail -3 "$O/bench.err"
+python - "$O/bench.json" <<'PY'
+import json, sys
+d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d['roofline']
 print('value', round(d['value'], 2), 'ms/step', round(d['ms_per_step'], 1), 'dominant', r['kernel'], 'profiles', r['profiles'])
 for n, k in r['kernels'].items():

@@ -6,7 +6,7 @@
 #   * more chain groups with more hardware queues (environment knobs only).
 # usage: gpurun --timeout 1500 -- 'bash tools/r03_final.sh'
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/final; mkdir -p $O; rm -f $O/*
-python bench.py --steps 2 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json
+python bench.py --full --steps 2 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json
 timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -3 | tee $O/parity.txt
 timeout 300 python __graft_entry__.py smoke 2>&1 | tail -2 | tee $O/smoke.txt
 prof() { # name, env/prefix...
