@@ -61,6 +61,7 @@
 #include <vector>
 
 #include "cmvm_core.h"
+#include "cmvm_geometry.h"
 #include "cmvm_gpu.h"
 #include "cmvm_host.h"
 
@@ -2784,12 +2785,6 @@ struct Carver {  // bump allocator over the arena; first pass sizes, second pass
     }
 };
 
-uint32_t pow2_ceil(uint64_t v) {
-    uint32_t p = 1;
-    while (p < v && p < (1u << 31)) p <<= 1;
-    return p;
-}
-
 }  // namespace
 
 struct PinnedBuffer {  // grow-only pinned host allocation reused across calls
@@ -3045,10 +3040,8 @@ void HipBackend::run_chains(const ChainJob *jobs, ChainOut *outs, int n) {
         g.pb_log2 = 5;  // payload line of a pair block: 16-byte header + Kpad u16 counts, padded to a power of two
         while ((1 << g.pb_log2) < 16 + 2 * g.Kpad) ++g.pb_log2;
         long long D0 = d.prep_digits;
-        // every greedy step removes at least one digit; typical chains need ~D0/8 steps
-        long long steps = jobs[i].method == M_DUMMY || jobs[i].method < 0 ? 0 : std::max<long long>(16, (long long)(D0 * row_scale_ / 4));
-        if (steps > D0) steps = std::max<long long>(D0, 1);
-        g.rcap = jobs[i].n_in + (int)steps + 1;
+        const TableGeometry tg = table_geometry(jobs[i], d.prep_pairs, D0, im.table_scale, row_scale_, MAX_GROUPS);
+        g.rcap = tg.rcap < (1 << REF_ROW_BITS) ? (int)tg.rcap : (1 << REF_ROW_BITS);
         g.lcap = jobs[i].n_in + d.prep_maxdcol + 1;
         g.pk_cap = (int)std::min<long long>(D0 + 1, (long long)1 << 30);  // digits only ever disappear
         // row lists: the dense lists of the input rows + one entry per (new row, column), each holding at least one of
@@ -3057,17 +3050,9 @@ void HipBackend::run_chains(const ChainJob *jobs, ChainOut *outs, int n) {
         if (rl_want >= (1ll << REF_OFF_BITS) || g.rcap >= (1 << REF_ROW_BITS) || jobs[i].n_out >= (1 << REF_LEN_BITS))
             throw std::runtime_error("problem too large for the row-reference format (rows < 2^24, columns < 4096, list entries < 2^28)");
         g.rl_cap = (uint32_t)rl_want;
-        // table capacity: blocks peak well above the initial pair count when rows are dense
-        long long pairs0 = std::min<long long>((long long)jobs[i].n_in * (jobs[i].n_in + 1) / 2, std::max<long long>(d.prep_pairs, 1));
-        double growth = std::max(4.0, jobs[i].n_in / 5.0);
-        double want = std::max(1024.0, 0.8 * pairs0 * growth * im.table_scale);
-        if (jobs[i].method == M_DUMMY) want = 64;
-        g.C = pow2_ceil((uint64_t)want);
-        g.gs_log2 = 8;
-        while ((g.C >> g.gs_log2) > (uint32_t)MAX_GROUPS) ++g.gs_log2;
-        if (g.gs_log2 > 14) throw std::runtime_error("pair table larger than 64M slots is not supported");
-        if (g.C < 256) g.C = 256;
-        g.n_groups = (int)(g.C >> g.gs_log2);
+        g.C = tg.C;
+        g.gs_log2 = tg.gs_log2;
+        g.n_groups = tg.n_groups;
         ChainDev tmp;
         a_off[i] = arena_bytes;
         arena_bytes += carve_chain(nullptr, jobs[i], g, tmp);
@@ -3079,7 +3064,10 @@ void HipBackend::run_chains(const ChainJob *jobs, ChainOut *outs, int n) {
         size_t budget = (size_t)(0.85 * (double)(free_b + im.arena.cap));
         if (const char *e = std::getenv("DA4ML_HIP_MEM_BUDGET_MB")) budget = (size_t)std::atoll(e) << 20;  // test hook
         if (arena_bytes > budget) {
-            if (n == 1) throw std::runtime_error("a single chain needs " + std::to_string(arena_bytes >> 20) + " MiB of device memory, more than is free");
+            if (n == 1)
+                throw std::runtime_error("a single chain needs " + std::to_string(arena_bytes >> 20) + " MiB of device memory (pair table of " +
+                                         std::to_string(geo[0].C) + " slots), " + std::to_string(free_b >> 20) + " MiB are free (budget " +
+                                         std::to_string(budget >> 20) + " MiB)");
             const int half_n = n / 2;
             run_chains(jobs, outs, half_n);
             run_chains(jobs + half_n, outs + half_n, n - half_n);
@@ -3590,22 +3578,17 @@ class HipShardEngine : public ShardEngine {
         g.pb_log2 = 5;
         while ((1 << g.pb_log2) < 16 + 2 * g.Kpad) ++g.pb_log2;
         const long long D0 = d_.prep_digits;
-        long long steps = std::max<long long>(16, (long long)(D0 * row_scale / 4));
-        if (steps > D0) steps = std::max<long long>(D0, 1);
-        g.rcap = job.n_in + (int)steps + 1;
+        const TableGeometry tg = table_geometry(job, d_.prep_pairs, D0, table_scale, row_scale, MAX_GROUPS);  // (the same function as run_chains)
+        g.rcap = tg.rcap < (1 << REF_ROW_BITS) ? (int)tg.rcap : (1 << REF_ROW_BITS);
         g.lcap = job.n_in + d_.prep_maxdcol + 1;
         g.pk_cap = (int)std::min<long long>(D0 + 1, (long long)1 << 30);
         const long long rl_want = (long long)job.n_in * n_loc_ + D0 + n_loc_ + 64;
         if (rl_want >= (1ll << REF_OFF_BITS) || g.rcap >= (1 << REF_ROW_BITS) || n_loc_ >= (1 << REF_LEN_BITS))
             throw std::runtime_error("problem too large for the row-reference format");
         g.rl_cap = (uint32_t)rl_want;
-        const long long pairs0 = std::min<long long>((long long)job.n_in * (job.n_in + 1) / 2, std::max<long long>(d_.prep_pairs, 1));
-        g.C = pow2_ceil((uint64_t)std::max(1024.0, 0.8 * pairs0 * std::max(4.0, job.n_in / 5.0) * table_scale));
-        g.gs_log2 = 8;
-        while ((g.C >> g.gs_log2) > (uint32_t)MAX_GROUPS) ++g.gs_log2;
-        if (g.gs_log2 > 14) throw std::runtime_error("pair table larger than 64M slots is not supported");
-        if (g.C < 256) g.C = 256;
-        g.n_groups = (int)(g.C >> g.gs_log2);
+        g.C = tg.C;
+        g.gs_log2 = tg.gs_log2;
+        g.n_groups = tg.n_groups;
         n_pairs_ = (long long)job.n_in * (job.n_in + 1) / 2;
         // arena: the chain's arrays (local column count) + the exchange buffers
         ChainJob local = job;
@@ -3614,7 +3597,15 @@ class HipShardEngine : public ShardEngine {
         const size_t chain_bytes = carve_chain(nullptr, local, g, tmp);
         const size_t init_b = align_up((size_t)n_pairs_ * g.K * 4, 256), flag_b = align_up((((size_t)g.rcap + 3) / 4 + SHARD_TRAILER) * 4 + 64, 256),
                      uni_b = align_up((size_t)g.rcap * 4, 256), slab_b = align_up((size_t)(6 + 3 * (size_t)g.rcap) * g.K * 4, 256);
-        arena_.get(chain_bytes + init_b + flag_b + uni_b + slab_b);
+        const size_t need = chain_bytes + init_b + flag_b + uni_b + slab_b;
+        {
+            size_t free_b = 0, total_b = 0;
+            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+            if (need > free_b)
+                throw std::runtime_error("a column-sharded chain needs " + std::to_string(need >> 20) + " MiB of device memory (pair table of " +
+                                         std::to_string(g.C) + " slots), " + std::to_string(free_b >> 20) + " MiB are free");
+        }
+        arena_.get(need);
         unsigned char *a = static_cast<unsigned char *>(arena_.ptr);
         carve_chain(a, local, g, d_);
         d_.cs_init = reinterpret_cast<int32_t *>(a + chain_bytes);

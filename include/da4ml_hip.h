@@ -12,6 +12,11 @@
  * The library never keeps pointers to caller memory after a call returns.
  *
  * Threading: calls are serialised per device by an internal mutex; solves of a batch run concurrently on the GPU.
+ *
+ * Size limits of a solve (DA_ERR_RUNTIME with a message beyond them): up to 2048 input rows are supported (pair tables of up to
+ * 2^30 slots; a chain whose arena does not fit into the free device memory is refused with the MiB it needs and the MiB that are
+ * free); n_out is limited to about 2300 by the selection kernel's LDS and to below 4096 by the row-reference format; a chain holds
+ * fewer than 2^24 rows and 2^28 row-list entries; at most 30 CSD digits per entry.
  */
 #ifndef DA4ML_HIP_H
 #define DA4ML_HIP_H
