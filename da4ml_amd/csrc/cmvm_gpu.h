@@ -10,7 +10,7 @@ namespace da {
 namespace gpu {
 
 struct GpuTimings {  // accumulated since the last reset; read by the benchmark harness
-    double loop_ms = 0;       // HIP-event time of the greedy loops (k_iter_select + k_iter_update launches)
+    double loop_ms = 0;       // HIP-event time of the greedy loops (k_iter_select2 + k_iter_update launches)
     double dist_ms = 0;       // HIP-event time of k_col_dist
     double total_ms = 0;      // wall time inside run_chains (uploads, set-up, loop, downloads)
     long long lockstep_iters = 0;  // launched (select, update) kernel pairs
@@ -20,7 +20,7 @@ struct GpuTimings {  // accumulated since the last reset; read by the benchmark 
     long long chains = 0;
     long long retries = 0;         // capacity retries (arena heuristics too small)
     long long dist_calls = 0;
-    // sampled per-kernel durations (HIP events around every 16th lockstep iteration)
+    // sampled per-kernel durations (HIP events around the first group's kernels in the first lockstep iteration of every window)
     double select_ms_sampled = 0, update_ms_sampled = 0;
     long long samples = 0;
     double sampled_chain_launches = 0;  // sum over sampled launches of the number of chains in that launch
@@ -28,10 +28,10 @@ struct GpuTimings {  // accumulated since the last reset; read by the benchmark 
     long long found = 0, inserts = 0, cell_reads = 0;
     double key_bytes = 0;     // 2 * K bytes per touched count block (u16 counts)
     double cell_bytes = 0;    // bytes of partner cells read
-    double phase_cycles[12] = {0};  // shader-clock cycles: k_iter_select phases 0-6, k_iter_update per-wave phases 7-11
+    double phase_cycles[12] = {0};  // shader-clock cycles: k_iter_select2 phases 0-6, k_iter_update per-wave phases 7-11
     double table_bytes = 0;   // bytes of pair-table storage summed over chains
     double arena_bytes = 0;   // largest device arena used
-    double select_bytes = 0;    // algorithmic bytes of k_iter_select, counted on the device
+    double select_bytes = 0;    // algorithmic bytes of k_iter_select2, counted on the device
     double host_launch_ms = 0;  // host time spent queueing the greedy loop's launches (the launch thread's share of the loop)
     long long fast_steps = 0;   // greedy steps whose pick was known before the step began (k_iter_select2)
     double search_diag[7] = {0};    // (phase-timer builds) re-reads of stale groups below the floor, of clean groups with an excluded best entry, rounds of the longest wave

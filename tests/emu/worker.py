@@ -95,6 +95,17 @@ def big_table():
     out(bad=bad)
 
 
+def sub_batch():
+    """a batch whose arena exceeds the memory budget (environment set by the test, tables inflated as in big_table) is halved
+    until the parts fit: every chain is solved once and counted once"""
+    o = Oracle('port')
+    ks = [int_matrix(20 + s, 8 + s % 3, 7 + s % 2, -64, 64) for s in range(5)] + [int_matrix(30, 6, 5, -8192, 8192)]
+    got = hip.solve_many(ks, **SINGLE)
+    bad = [i for i, k in enumerate(ks) if got[i] != o.solve(k, **SINGLE)]
+    tm = hip.timings()
+    out(bad=bad, n=len(ks), chains=tm['chains'], arena_mib=tm['arena_bytes'] / 2**20)
+
+
 def record(name, fname):
     """a committed large record (tests/golden/large_*_golden.json: 128x128 / 256x256 chains and default searches, made by the
     oracle or by oracle/_ref/libref.so in up to 141 minutes of CPU) reproduced by the kernels on the emulated device"""
@@ -177,7 +188,7 @@ def retry():
 
 
 def shard_single():
-    """the column-sharded engine (k_cs_* kernels, k_iter_select<SHARDED>) with one rank: exchanges are no-ops"""
+    """the column-sharded engine (k_cs_* kernels, k_iter_select2<Cell, SHARDED>) with one rank: exchanges are no-ops"""
     o = Oracle('port')
     bad = []
     for seed, shape in ((1, (10, 12)), (2, (7, 5)), (3, (4, 300))):
@@ -267,5 +278,5 @@ def dais():
 
 if __name__ == '__main__':
     what = sys.argv[1]
-    {'random': lambda: random_cases(int(sys.argv[2]), int(sys.argv[3])), 'oddsteps': lambda: odd_steps(int(sys.argv[2]), int(sys.argv[3])), 'layouts': layouts, 'batch': batch, 'lds_budget': lds_budget, 'retry': retry, 'big_table': big_table, 'fork': fork_after_use, 'record': lambda: record(sys.argv[2], sys.argv[3]),
+    {'random': lambda: random_cases(int(sys.argv[2]), int(sys.argv[3])), 'oddsteps': lambda: odd_steps(int(sys.argv[2]), int(sys.argv[3])), 'layouts': layouts, 'batch': batch, 'lds_budget': lds_budget, 'retry': retry, 'big_table': big_table, 'sub_batch': sub_batch, 'fork': fork_after_use, 'record': lambda: record(sys.argv[2], sys.argv[3]),
      'shard_single': shard_single, 'shard_retry': shard_retry, 'shard_rank': shard_rank, 'dais': dais, 'race_cases': race_cases}[what]()  # fmt: skip

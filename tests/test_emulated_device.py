@@ -92,6 +92,16 @@ def test_table_geometry_of_a_large_chain(emu):
     assert emu('big_table', env=dict(DA4ML_HIP_TABLE_SCALE='6000'))['bad'] == []
 
 
+def test_sub_batching_under_memory_pressure(emu):
+    """a batch whose arena exceeds the device-memory budget is halved until the parts fit (the GPU suite's test of the same name, on the
+    emulated device).  With the tables inflated by DA4ML_HIP_TABLE_SCALE the six chains need 14.4 MiB together and 2.2 to 4.4 MiB each: under a
+    budget of 6 MiB the batch splits twice (6 -> 3 + 3 -> 1 + 2 each); every chain is solved once, counted once, and equals the oracle's"""
+    whole = emu('sub_batch', env=dict(DA4ML_HIP_TABLE_SCALE='100'))
+    split = emu('sub_batch', env=dict(DA4ML_HIP_TABLE_SCALE='100', DA4ML_HIP_MEM_BUDGET_MB='6'))
+    assert whole['bad'] == [] and whole['chains'] == whole['n'] == 6 and whole['arena_mib'] > 6
+    assert split['bad'] == [] and split['chains'] == split['n'] == 6 and split['arena_mib'] <= 6
+
+
 @pytest.mark.skipif(not os.environ.get('DA4ML_EMU_SLOW'), reason='minutes to half an hour per record: set DA4ML_EMU_SLOW=1 (run before every hand-over of kernel changes that no GPU has seen)')
 @pytest.mark.parametrize('name,fname', [('128x128_seed0_single_chain_ref', 'large_chain_golden.json'), ('64x64_seed0_default', 'large_default_golden.json'),
                                         ('256x256_seed0_single_chain', 'large_chain_golden.json')])  # fmt: skip
@@ -102,7 +112,7 @@ def test_large_records_on_the_emulated_device(emu, name, fname):
 
 
 def test_column_sharded_engine_single_rank(emu):
-    """HipShardEngine (k_cs_init_counts, k_cs_init_table, k_iter_select<SHARDED>, k_cs_union, k_cs_partial, k_cs_apply)"""
+    """HipShardEngine (k_cs_init_counts, k_cs_init_table, k_iter_select2<Cell, SHARDED>, k_cs_union, k_cs_partial, k_cs_apply)"""
     assert emu('shard_single', env=dict(DA4ML_SHARD_FORCE='1'))['bad'] == []
 
 
