@@ -37,7 +37,7 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    # the greedy loop's launches are queued by two host threads that never block (csrc/cmvm_engine.hip, HipBackend::run_chains): with
+    # the greedy loop's launches are queued by two host threads that never block (csrc/hip_batch.h, HipBackend::run_chains): with
     # fewer than three cores to run on they would take turns on one another's time slices -- one thread then (the backend reads this when
     # it is created; an explicit setting wins)
     try:

@@ -1,6 +1,7 @@
-// cmvm_engine.hip -- hand-written HIP kernels (gfx950 / CDNA4, wave64) for the CMVM greedy engine and
-// the HIP implementation of da::Backend.  No CUDA compatibility layer, no dual paths: this file only
-// targets MI355X.
+// cmvm_engine.hip -- hand-written HIP kernels (gfx950 / CDNA4, wave64) for the CMVM greedy engine.  No CUDA
+// compatibility layer, no dual paths: this file only targets MI355X.
+// DEVICE CODE ONLY: bench.py's source_digest() hashes this file as what the kernels are compiled from, so a host edit must not
+// touch it.  The HIP implementation of da::Backend that launches them is in the hip_*.h headers included at the end of the file.
 //
 // Reference loops replaced:
 //   k_prepare        _center + global digit width            bit_decompose.hh:25-34, bit_decompose.cc:22-27
@@ -13,7 +14,7 @@
 //   k_extract        digit gather of to_solution             cmvm_core.cc:103-113
 //   k_col_dist       stage-1 CSD Hamming distances           mat_decompose.cc:75-93
 //
-// Data layout in HBM, per chain (all arrays carved from one arena, see HipBackend::run_chains):
+// Data layout in HBM, per chain (all arrays carved from one arena, see carve_chain in hip_chain_setup.h):
 //   rlist   row lists: every row is a list of (column, cell) entries sorted by column.  The n_in input rows are DENSE
 //           (n_out entries, entry j = column j); every later row is SPARSE: it only ever holds the columns it was
 //           created with (digits only disappear from a row), so a typical row is one 128-byte line.  A cell holds the
@@ -67,13 +68,6 @@
 
 namespace da {
 namespace gpu {
-
-#define HIP_CHECK(expr)                                                                                          \
-    do {                                                                                                         \
-        hipError_t _e = (expr);                                                                                  \
-        if (_e != hipSuccess)                                                                                    \
-            throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " at " #expr);         \
-    } while (0)
 
 constexpr uint64_t KEY_EMPTY = ~0ull;
 // Tombstones carry the low two bits of the launch that wrote them (KEY_TOMB - id, id = 0..3).  A slot freed in a
@@ -583,17 +577,9 @@ __device__ __forceinline__ void group_note(const Ctx &c, int slot, unsigned long
     const int grp = slot >> c.gs_log2;
     if (w_new > w_old) {
         atomicMax(gen(&c.grec[grp].ub), w_new);
-#ifdef DA_AB_PLAIN_FLAG
-        c.grec[grp].dirty = 1u;
-#else
-        atomicOr(gen(&c.grec[grp].dirty), 1u);
-#endif
+        atomicOr(gen(&c.grec[grp].dirty), 1u);  // (a plain store of the flag and the lazy scheme without glow were A/B variants of round 6: profiles/r06_ab_engine.txt)
     } else {
-#ifdef DA_AB_NO_GLOW  // (A/B: the lazy scheme -- still exact, stale bounds are found when the floor meets them)
-        c.grec[grp].dirty = 1u;
-#else
         atomicMax(gen(&c.grec[grp].glow), w_old);
-#endif
     }
 }
 // one lane: the best entry (rank > 0) of a block as it stands after this launch -- a candidate for the next pick if it reaches the
@@ -1198,9 +1184,7 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
                 const bool own_dirty = (((uint32_t)__builtin_amdgcn_readlane((int)dmask, owner) >> own_u) & 1u) != 0;
                 read_group((uint32_t)(wid * GPW + owner + own_u * WAVE), own_dirty, wtop, fl);
                 if (lane == owner) q_ub[own_u][tid] = 0;
-            }
-#ifndef DA_AB_NO_IDLE_REPAIR
-            else {  // nothing of its own to read: one of the groups with a stale bound, if there are any
+            } else {  // nothing of its own to read: one of the groups with a stale bound, if there are any (A/B of round 6: profiles/r06_ab_engine.txt)
                 unsigned int k = 0;
                 if (lane == 0) k = atomicAdd(&q_stake, 1u);
                 k = (unsigned int)__builtin_amdgcn_readfirstlane((int)k);
@@ -1210,7 +1194,6 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
                     read_group((uint32_t)((t / WAVE) * GPW + (t % WAVE) + u * WAVE), true, 0ull, fl);
                 }
             }
-#endif
         }
         __syncthreads();
         // ---- the groups that still reach the floor, from all waves into one work list, dealt out evenly: a wave that owns several of them
@@ -2718,1191 +2701,13 @@ __global__ void __launch_bounds__(256) k_absmax(const int32_t *x, long long n, u
 }
 
 // =================================================================================================== host side
-
-namespace {
-
-struct DeviceBuffer {  // grow-only device allocation reused across calls
-    void *ptr = nullptr;
-    size_t cap = 0;
-    void *get(size_t bytes) {
-        if (bytes > cap) {
-            if (ptr) (void)hipFree(ptr);
-            ptr = nullptr;
-            cap = 0;
-            size_t want = bytes + bytes / 8;
-            HIP_CHECK(hipMalloc(&ptr, want));
-            cap = want;
-        }
-        return ptr;
-    }
-    ~DeviceBuffer() {
-        if (ptr) (void)hipFree(ptr);
-    }
-};
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// spin-wait step of the two launch threads' hand-shake: a pause for the first few thousand polls (the partner answers within microseconds while both are
-// queueing launches), then the core is given up between polls -- the waits that last (the main thread waiting for the device, the helper between
-// windows) must not hold a core at 100 % (ranks of one host share its cores)
-inline void spin_wait_step(unsigned &polls) {
-    if (++polls < 4096u) {
-#if defined(__x86_64__) || defined(__i386__)
-        __builtin_ia32_pause();
-#elif defined(__aarch64__)
-        asm volatile("yield");
-#endif
-    } else if (polls < 8192u)
-        std::this_thread::yield();
-    else
-        std::this_thread::sleep_for(std::chrono::microseconds(50));
-}
-
-// Events of one call, destroyed however the call ends (a HIP error or the termination guard of the greedy loop used to leak
-// the timing, window and sample events of the call -- up to 12 k of them).
-struct EventGuard {
-    std::vector<hipEvent_t> all;
-    hipEvent_t make(unsigned flags = 0) {
-        hipEvent_t e = nullptr;
-        HIP_CHECK(flags ? hipEventCreateWithFlags(&e, flags) : hipEventCreate(&e));
-        all.push_back(e);
-        return e;
-    }
-    ~EventGuard() {
-        for (hipEvent_t e : all) (void)hipEventDestroy(e);
-    }
-};
-
-struct Carver {  // bump allocator over the arena; first pass sizes, second pass assigns
-    unsigned char *base;
-    size_t off = 0;
-    explicit Carver(unsigned char *b) : base(b) {}
-    template <class T> T *take(size_t count) {
-        off = align_up(off, 256);
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
-}  // namespace
-
-struct PinnedBuffer {  // grow-only pinned host allocation reused across calls
-    void *ptr = nullptr;
-    size_t cap = 0;
-    void *get(size_t bytes) {
-        if (bytes > cap) {
-            if (ptr) (void)hipHostFree(ptr);
-            ptr = nullptr;
-            cap = 0;
-            size_t want = bytes + bytes / 4 + 4096;
-            HIP_CHECK(hipHostMalloc(&ptr, want, hipHostMallocDefault));
-            cap = want;
-        }
-        return ptr;
-    }
-    ~PinnedBuffer() {
-        if (ptr) (void)hipHostFree(ptr);
-    }
-};
-
-struct HipBackend::Impl {
-    int device = 0;
-    PinnedBuffer pinned, pinned_up;  // staging of the downloads / of the upload
-    hipStream_t stream = nullptr;
-    static constexpr int MAX_LANES = 8;
-    hipStream_t lanes[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // greedy-loop streams of the chain groups
-    int launch_threads = 2;  // host threads queueing the greedy loop's launches (each its share of the chain groups); DA4ML_HIP_LAUNCH_THREADS
-    int n_lanes = 4;  // chain groups = greedy-loop streams.  Measured (C3 batch 64, loop ms): 2 -> 880, 3 -> 871, 4 -> 838, 5..8 -> 1470:
-                      // four hardware queues; the poll stream's rare copies share one of them at no visible cost
-    int upd_total_blocks = 2560;  // k_iter_update blocks over all chains of a batch (4 waves x 4 groups each); measured (C3 batch 64,
-                                  // solves/s): 1024: 45.3, 1536: 53.3, 2048: 53.8, 2560: 55.5, 4096: 47.5
-    DeviceBuffer arena, desc_buf, io_buf, gather_buf, piece_buf;  // gather_buf: the results of a batch, contiguous, before they leave
-    unsigned int *d_done = nullptr;
-    unsigned int *h_done = nullptr;  // pinned, two words: done counters of alternating poll windows
-    hipStream_t poll_stream = nullptr;
-    GpuTimings timings;
-    double table_scale = 1.0;  // grows on E_TABLE_CAPACITY retries
-    struct Batch;  // the state of one run_chains call
-};
-
-HipBackend::HipBackend(int device) : impl_(new Impl) {
-    impl_->device = device;
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&impl_->stream, hipStreamNonBlocking));
-    impl_->lanes[0] = impl_->stream;  // the first group runs on the main stream (hardware queues are a scarce resource)
-    for (int l = 1; l < Impl::MAX_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&impl_->lanes[l], hipStreamNonBlocking));
-    if (const char *e = std::getenv("DA4ML_HIP_TABLE_SCALE")) impl_->table_scale = std::max(1e-4, std::atof(e));
-    if (const char *e = std::getenv("DA4ML_HIP_ROW_SCALE")) row_scale_ = std::max(1e-4, std::atof(e));
-    if (const char *e = std::getenv("DA4ML_HIP_UPD_BLOCKS")) impl_->upd_total_blocks = std::max(2, std::atoi(e));
-    if (const char *e = std::getenv("DA4ML_HIP_LAUNCH_THREADS")) impl_->launch_threads = std::max(1, std::atoi(e));
-    if (const char *e = std::getenv("DA4ML_HIP_LANES")) impl_->n_lanes = std::max(1, std::min((int)Impl::MAX_LANES, std::atoi(e)));
-    HIP_CHECK(hipMalloc(&impl_->d_done, sizeof(unsigned int)));
-    HIP_CHECK(hipHostMalloc(&impl_->h_done, 2 * sizeof(unsigned int), hipHostMallocDefault));
-    HIP_CHECK(hipStreamCreateWithFlags(&impl_->poll_stream, hipStreamNonBlocking));
-    Log2Table t = measure_log2_table();
-    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_log2), &t, sizeof t));
-}
-HipBackend::~HipBackend() {
-    (void)hipSetDevice(impl_->device);
-    if (impl_->d_done) (void)hipFree(impl_->d_done);
-    if (impl_->h_done) (void)hipHostFree(impl_->h_done);
-    if (impl_->poll_stream) (void)hipStreamDestroy(impl_->poll_stream);
-    if (impl_->stream) (void)hipStreamDestroy(impl_->stream);
-    for (int l = 1; l < Impl::MAX_LANES; ++l)
-        if (impl_->lanes[l]) (void)hipStreamDestroy(impl_->lanes[l]);
-}
-const GpuTimings &HipBackend::timings() const { return impl_->timings; }
-void HipBackend::reset_timings() { impl_->timings = GpuTimings{}; }
-void *HipBackend::stream() const { return impl_->stream; }
-
-namespace {
-
-struct Geometry {
-    bool wide;  // 64-bit cells and 16-byte list entries (more than 12 digits or more than 256 columns)
-    int n_mant = 0;  // distinct non-power-of-two step mantissas of the inputs (StepLog2): rows of the -log2f table
-    int n_bits, K, Kpad, rcap, lcap, gs_log2, n_groups, pk_cap, pb_log2;
-    uint32_t C, rl_cap;
-};
-
-// `wide` (and a flag) as template arguments: f is called with a value of the cell type (with std::true_type / std::false_type)
-template <class F> void with_cell(bool wide, F &&f) {
-    if (!wide)
-        f(uint32_t{});
-    else
-        f(uint64_t{});
-}
-template <class F> void with_flag(bool on, F &&f) {
-    if (!on)
-        f(std::false_type{});
-    else
-        f(std::true_type{});
-}
-// raises the dynamic-LDS limit of the selection kernel the chains of that width are about to be launched with
-template <bool SHARDED> void sel2_allow_lds(bool wide, size_t bytes) {
-    with_cell(wide, [&](auto c) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_select2<decltype(c), SHARDED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    });
-}
-
-// f(0) .. f(n - 1) on a few host threads, the caller among them: min(n, 8, one per MiB of `bytes` moved); the first exception is rethrown here
-template <class F> void parallel_for(int n, size_t bytes, F &&f) {
-    const int workers = (int)std::min<size_t>({(size_t)n, (size_t)8, bytes / (1u << 20) + 1});
-    std::atomic<int> next{0};
-    std::exception_ptr err;
-    std::mutex err_mu;
-    auto work = [&] {
-        try {
-            for (int i = next++; i < n; i = next++) f(i);
-        } catch (...) {
-            std::lock_guard<std::mutex> lk(err_mu);
-            if (!err) err = std::current_exception();
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < workers; ++t) pool.emplace_back(work);
-    work();
-    for (auto &t : pool) t.join();
-    if (err) std::rethrow_exception(err);
-}
-
-// Byte offsets of a chain's inputs in an io buffer: kernel | qints | lats | xint (the centred matrix, written by k_prepare) | shift0 | shift1, each
-// rounded to 256 bytes.  Without `lats` (csd_decompose) that part is empty.
-struct InputLayout {
-    size_t kernel = 0, qints, lats, xint, shift0, shift1, bytes;
-};
-InputLayout input_layout(int n_in, int n_out, bool lats = true) {
-    const size_t e = (size_t)n_in * n_out;
-    InputLayout L;
-    L.qints = align_up(e * 4, 256);
-    L.lats = L.qints + align_up((size_t)n_in * 12, 256);
-    L.xint = L.lats + (lats ? align_up((size_t)n_in * 4, 256) : 0);
-    L.shift0 = L.xint + align_up(e * 4, 256);
-    L.shift1 = L.shift0 + align_up(n_in, 256);
-    L.bytes = L.shift1 + align_up(n_out, 256);
-    return L;
-}
-
-// The job fields of a descriptor, all else zero: the chain holds the `n_loc` columns from `col0` on of the job's matrix, whose inputs are at `io`
-void fill_job(ChainDev &d, const ChainJob &j, int n_loc, int col0, unsigned char *io, const InputLayout &L) {
-    std::memset(&d, 0, sizeof d);
-    d.n_in = j.n_in;
-    d.n_out = n_loc;
-    d.pn_out = j.n_out;
-    d.col0 = col0;
-    d.method = j.method;
-    d.adder_size = j.adder_size;
-    d.carry_size = j.carry_size;
-    d.kernel = reinterpret_cast<const float *>(io + L.kernel);
-    d.qints = reinterpret_cast<const float *>(io + L.qints);
-    d.lats = reinterpret_cast<const float *>(io + L.lats);
-    d.xint = reinterpret_cast<int32_t *>(io + L.xint);
-    d.shift0 = reinterpret_cast<int8_t *>(io + L.shift0);
-    d.shift1 = reinterpret_cast<int8_t *>(io + L.shift1);
-}
-
-// Dynamic LDS of a k_iter_select2 block WITHOUT the optional claim area (pick_body's carve): B's list, six count vectors, five per-column arrays
-size_t sel2_fixed_lds(int n_out, const Geometry &g) {
-    const size_t no = (size_t)n_out, entb = g.wide ? 16 : 4;
-    return no * entb + 6 * (size_t)g.Kpad * 4 + (5 * no + 1) * 4;
-}
-// What the device leaves for it: the per-workgroup LDS limit less the kernel's STATIC __shared__ arrays (the search block's bound / work lists,
-// the substitution block's partner ids: ~75 KB -- asked from the runtime, not assumed), less a small reserve.  Static + dynamic beyond the limit
-// fails in hipFuncSetAttribute or at launch with a raw HIP error; the caller turns it into a clear message.
-size_t sel2_lds_budget(int device, bool wide) {
-    static std::mutex mu;
-    static size_t cached[2] = {0, 0};
-    std::lock_guard<std::mutex> lk(mu);
-    if (!cached[wide]) {
-        hipFuncAttributes fa;
-        const void *fn = wide ? reinterpret_cast<const void *>(&k_iter_select2<uint64_t>) : reinterpret_cast<const void *>(&k_iter_select2<uint32_t>);
-        HIP_CHECK(hipFuncGetAttributes(&fa, fn));
-        int limit = 0;
-        HIP_CHECK(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
-        if (limit < 64 * 1024) limit = 64 * 1024;
-        const size_t used = fa.sharedSizeBytes + 256;
-        cached[wide] = (size_t)limit > used ? (size_t)limit - used : 1;
-    }
-    return cached[wide];
-}
-// words of the optional LDS area in which the substitution block combines the row bitmaps of a young chain: dropped (0: every wave ORs its words
-// itself) when it does not fit beside the rest -- the kernel runs either way
-int claim_words_for(int n_out, const Geometry &g, size_t budget) {
-    const size_t words = ((size_t)g.rcap + 31) / 32, fixed = align_up(sel2_fixed_lds(n_out, g), 16);
-    return words * 4 <= 64 * 1024 && fixed + words * 4 + 16 <= budget ? (int)words : 0;
-}
-
-// The two range errors of derive_geometry, worded by its caller (the batch and the column-sharded chain word them differently)
-struct GeometryErrors {
-    const char *digits, *row_ref;
-};
-// Geometry of a chain of `n_loc` columns (all of the job's in a batch, a rank's slice in a column-sharded chain) from its prepared descriptor:
-// k_prepare's statistics are those of the whole matrix, as is the pair table
-Geometry derive_geometry(const ChainDev &d, const ChainJob &job, int n_loc, int n_mant, double table_scale, double row_scale, const GeometryErrors &msg) {
-    Geometry g;
-    g.n_bits = d.prep_nbits;
-    if (g.n_bits > 30) throw std::runtime_error(msg.digits);
-    g.wide = g.n_bits > 12 || n_loc > 256;  // the narrow list entry is col:8 | minus:12 | plus:12
-    g.n_mant = n_mant;
-    g.K = key_count(g.n_bits);
-    g.Kpad = (g.K + 3) & ~3;
-    g.pb_log2 = 5;  // payload line of a pair block: 16-byte header + Kpad u16 counts, padded to a power of two
-    while ((1 << g.pb_log2) < 16 + 2 * g.Kpad) ++g.pb_log2;
-    const long long D0 = d.prep_digits;
-    const TableGeometry tg = table_geometry(job, d.prep_pairs, D0, table_scale, row_scale, MAX_GROUPS);
-    g.rcap = tg.rcap < (1 << REF_ROW_BITS) ? (int)tg.rcap : (1 << REF_ROW_BITS);
-    g.lcap = job.n_in + d.prep_maxdcol + 1;
-    g.pk_cap = (int)std::min<long long>(D0 + 1, (long long)1 << 30);  // digits only ever disappear
-    // row lists: the dense lists of the input rows + one entry per (new row, column), each holding at least one of
-    // the digits that the substitutions move into new rows (at most D0 over a chain)
-    const long long rl_want = (long long)job.n_in * n_loc + D0 + n_loc + 64;
-    if (rl_want >= (1ll << REF_OFF_BITS) || g.rcap >= (1 << REF_ROW_BITS) || n_loc >= (1 << REF_LEN_BITS)) throw std::runtime_error(msg.row_ref);
-    g.rl_cap = (uint32_t)rl_want;
-    g.C = tg.C;
-    g.gs_log2 = tg.gs_log2;
-    g.n_groups = tg.n_groups;
-    return g;
-}
-
-// carve one chain's arrays; with base == nullptr only the size is computed
-size_t carve_chain(unsigned char *base, int n_loc, const Geometry &g, ChainDev &d) {
-    Carver c(base);
-    size_t cell = g.wide ? 8 : 4, entry = g.wide ? 16 : 4;
-    size_t n_out = n_loc;
-    d.rlist = c.take<unsigned char>((size_t)g.rl_cap * entry);
-    d.rowoff = c.take<da_u2>(g.rcap);
-    d.rows = c.take<RowInfo>(g.rcap);
-    d.stamp = c.take<uint32_t>(g.rcap);
-    d.collist = c.take<unsigned long long>(n_out * (size_t)g.lcap);
-    d.collen = c.take<int>(n_out);
-    d.hkey = c.take<unsigned long long>(g.C);
-    d.hrank = c.take<uint32_t>((size_t)g.C + ((size_t)g.C + 3) / 4);  // + the best-key indices, one byte per slot, right behind the ranks (hidx_ptr)
-    d.hblk = c.take<unsigned char>((size_t)g.C << g.pb_log2);
-    d.grec = c.take<GroupRec>(g.n_groups);
-    d.mcol = c.take<int>(n_out);
-    d.cmap = c.take<uint16_t>(n_out);
-    d.colbits = c.take<uint32_t>(n_out * (size_t)((g.rcap + 31) / 32));
-    d.pl_ids = c.take<uint32_t>(g.rcap);
-    d.mA = c.take<unsigned char>(n_out * cell);
-    d.mB = c.take<unsigned char>(n_out * cell);
-    d.plist = c.take<unsigned long long>(g.rcap);
-    d.sp_cnt = c.take<uint32_t>((size_t)6 * g.Kpad);
-    d.picks = c.take<int4>(g.rcap);
-    d.fin_row = c.take<uint32_t>(n_out * (size_t)g.lcap);
-    d.fin_cell = c.take<unsigned long long>(n_out * (size_t)g.lcap);
-    d.fin_count = c.take<uint32_t>(n_out);
-    d.fin_start = c.take<uint32_t>(n_out + 1);
-    d.pk_cap = g.pk_cap;
-    d.pk_row = c.take<uint32_t>((size_t)g.pk_cap);
-    d.pk_cell = c.take<unsigned long long>((size_t)g.pk_cap);
-    d.pk_lat = c.take<float>(g.rcap);
-    d.step_mant = c.take<uint32_t>((size_t)std::max(g.n_mant, 1));  // filled only when an input step is not a power of two (StepLog2)
-    d.step_tab = c.take<float>((size_t)std::max(g.n_mant, 1) * 256);
-    return align_up(c.off, 256);
-}
-
-// The geometry into a descriptor whose job fields are set and whose arrays carve_chain has assigned: the chain before its first step
-void apply_geometry(ChainDev &d, const Geometry &g, size_t lds_budget) {
-    d.n_bits = g.n_bits;
-    d.K = g.K;
-    d.Kpad = g.Kpad;
-    d.rcap = g.rcap;
-    d.lcap = g.lcap;
-    d.gs_log2 = g.gs_log2;
-    d.n_groups = g.n_groups;
-    d.C = g.C;
-    d.cmask = g.C - 1;
-    d.pb_log2 = g.pb_log2;
-    d.rl_cap = g.rl_cap;
-    d.rl_used = (uint32_t)d.n_in * (uint32_t)d.n_out;
-    d.n_rows = d.n_in;
-    d.claim_words = claim_words_for(d.n_out, g, lds_budget);
-    d.iter = 0;
-    d.cb_words = (g.rcap + 31) / 32;
-    d.n_step_mant = g.n_mant;
-}
-// -log2f tables of non-power-of-two input steps into the chain's arena; `t` is read by asynchronous copies: the caller keeps it until `st` has been synchronised
-void upload_step_table(const ChainDev &d, const StepLog2Host &t, hipStream_t st) {
-    if (!d.n_step_mant) return;
-    HIP_CHECK(hipMemcpyAsync(const_cast<uint32_t *>(d.step_mant), t.mant.data(), t.mant.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(const_cast<float *>(d.step_tab), t.tab.data(), t.tab.size() * 4, hipMemcpyHostToDevice, st));
-}
-
-// What a chain reports of itself, from its final descriptor
-void fill_result(ChainOut &o, const ChainDev &d) {
-    o = ChainOut{};
-    o.error = d.error;
-    o.unknown_method_hit = d.unknown_hit != 0;
-    o.n_bits = d.n_bits;
-    o.stats.iterations = d.iter;
-    o.stats.digits0 = d.prep_digits;
-    o.stats.table_peak = d.live_peak;
-    o.stats.scan_slots = (long long)d.st_rescans << d.gs_log2;
-    o.stats.partners = (long long)d.st_partners;
-    o.stats.matches = (long long)d.st_matches;
-}
-
-}  // namespace
-
-// One call of run_chains: what its phases, in the order of their definition, hand to each other.
-struct HipBackend::Impl::Batch {
-    Impl &im;
-    const ChainJob *const jobs;
-    ChainOut *const outs;
-    const int n;
-    const hipStream_t st;
-    Batch(Impl &impl, const ChainJob *j, ChainOut *o, int count) : im(impl), jobs(j), outs(o), n(count), st(impl.stream) {}
-
-    // Pageable host memory that asynchronous copies on `st` read or write.  Each stays alive until the stream's next synchronise, which may come
-    // in a later phase or, after an exception, not at all: they are members, never locals of a phase.
-    std::vector<ChainDev> desc, sorted, fin;  // descriptors: as prepared and set up (job order) | sorted by width (only when that differs) | final (sorted order)
-    // -log2f tables of non-power-of-two input steps (rare: the tracer's `variable * 3`), by the host libm, one row per distinct
-    // mantissa -- as many as the inputs have (the reference takes log2 of any step, state_opr.cc:57); they stay alive until the
-    // set-up stream has been synchronised at the end of init_chains
-    std::vector<StepLog2Host> step_tabs;
-    std::vector<GatherPiece> pieces;
-
-    ChainDev *d_desc = nullptr;
-    int max_n_out = 0;
-    std::vector<Geometry> geo;
-    std::vector<size_t> a_off;  // of every chain in the arena
-    size_t arena_bytes = 0, budget = 0, free_b = 0;
-    std::vector<int> order;  // descriptor s of the device is chain order[s] of the call: narrow chains first
-    struct Range {
-        int first, count;
-        bool wide;
-    } ranges[2];
-    size_t sel_lds[2] = {0, 0}, upd_lds[2] = {0, 0};  // per width: dynamic LDS of the loop's kernels, k_iter_update blocks per chain
-    int upd_blocks[2] = {1, 1};
-    EventGuard events;  // declared before anything greedy_loop declares: destroyed after its streams have been drained, and after extract has read the clocks
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<hipEvent_t> sample_ev;  // three per sampled iteration
-    int sampled_chains = 0;  // chains of the group whose kernels are sampled
-    long long launched_iters = 0;
-    double host_launch_ms = 0;  // host time spent queueing launches (not waiting for the device)
-    float loop_ms = 0;
-
-    // ---- 1. inputs to the device, k_prepare
-    void upload_and_prepare() {
-        std::vector<size_t> in_off(n);
-        size_t in_bytes = 0;
-        for (int i = 0; i < n; ++i) {
-            in_off[i] = in_bytes;
-            in_bytes += input_layout(jobs[i].n_in, jobs[i].n_out).bytes;
-            max_n_out = std::max(max_n_out, jobs[i].n_out);
-        }
-        unsigned char *io = static_cast<unsigned char *>(im.io_buf.get(std::max<size_t>(in_bytes, 256)));
-        unsigned char *stage_ptr = static_cast<unsigned char *>(im.pinned_up.get(std::max<size_t>(in_bytes, 256)));  // pinned: the upload is one asynchronous DMA
-        desc.resize(n);
-        // the inputs into the pinned staging buffer, on a few host threads (16 MB for the 64 matrices of the benchmark)
-        parallel_for(n, in_bytes, [&](int i) {
-            const ChainJob &j = jobs[i];
-            const InputLayout L = input_layout(j.n_in, j.n_out);
-            fill_job(desc[i], j, j.n_out, 0, io + in_off[i], L);
-            std::memcpy(stage_ptr + in_off[i] + L.kernel, j.kernel, (size_t)j.n_in * j.n_out * 4);
-            std::memcpy(stage_ptr + in_off[i] + L.qints, j.qints, (size_t)j.n_in * 12);
-            std::memcpy(stage_ptr + in_off[i] + L.lats, j.lats, (size_t)j.n_in * 4);
-        });
-        HIP_CHECK(hipMemcpyAsync(io, stage_ptr, in_bytes, hipMemcpyHostToDevice, st));
-        d_desc = static_cast<ChainDev *>(im.desc_buf.get(sizeof(ChainDev) * (size_t)n));
-        HIP_CHECK(hipMemcpyAsync(d_desc, desc.data(), sizeof(ChainDev) * (size_t)n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_prepare, dim3(n), dim3(256), (size_t)max_n_out * 4, st, d_desc);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(desc.data(), d_desc, sizeof(ChainDev) * (size_t)n, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-
-    // ---- 2. geometry of every chain, size of the arena and what device memory allows; nothing is queued
-    void plan(double row_scale) {
-        static const GeometryErrors msg{"kernel needs more than 30 CSD digits per entry (the reference overflows int32 there); unsupported",
-                                        "problem too large for the row-reference format (rows < 2^24, columns < 4096, list entries < 2^28)"};
-        step_tabs.resize(n);
-        for (int i = 0; i < n; ++i)
-            if (jobs[i].adder_size >= 0 || jobs[i].carry_size >= 0) step_tabs[i].build(jobs[i].qints, jobs[i].n_in);  // (latency model off: steps are never looked at)
-        geo.resize(n);
-        a_off.resize(n);
-        for (int i = 0; i < n; ++i) {
-            geo[i] = derive_geometry(desc[i], jobs[i], jobs[i].n_out, (int)step_tabs[i].mant.size(), im.table_scale, row_scale, msg);
-            ChainDev tmp;
-            a_off[i] = arena_bytes;
-            arena_bytes += carve_chain(nullptr, jobs[i].n_out, geo[i], tmp);
-        }
-        size_t total_b = 0;
-        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        budget = (size_t)(0.85 * (double)(free_b + im.arena.cap));
-        if (const char *e = std::getenv("DA4ML_HIP_MEM_BUDGET_MB")) budget = (size_t)std::atoll(e) << 20;  // test hook
-    }
-
-    // ---- 3. arena, descriptors, initial state; launch sizes per cell width (descriptors are grouped so that one launch covers a contiguous range)
-    void init_chains() {
-        unsigned char *arena = static_cast<unsigned char *>(im.arena.get(arena_bytes));
-        for (int i = 0; i < n; ++i) {
-            carve_chain(arena + a_off[i], jobs[i].n_out, geo[i], desc[i]);
-            apply_geometry(desc[i], geo[i], sel2_lds_budget(im.device, geo[i].wide));
-            desc[i].done = (jobs[i].method == M_DUMMY || jobs[i].method < 0) ? 1 : 0;
-        }
-        for (int i = 0; i < n; ++i) upload_step_table(desc[i], step_tabs[i], st);
-        HIP_CHECK(hipMemcpyAsync(d_desc, desc.data(), sizeof(ChainDev) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemsetAsync(im.d_done, 0, sizeof(unsigned int), st));
-        // initial state of all chains in ONE launch (was six hipMemsetAsync per chain: 384 calls and 384 small kernels per batch)
-        hipLaunchKernelGGL(k_init_state, dim3(128, n), dim3(256), 0, st, d_desc);
-        HIP_CHECK(hipGetLastError());
-
-        order.resize(n);
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return geo[a].wide < geo[b].wide; });
-        bool permuted = false;
-        for (int i = 0; i < n; ++i) permuted |= order[i] != i;
-        if (permuted) {
-            sorted.resize(n);
-            for (int i = 0; i < n; ++i) sorted[i] = desc[order[i]];
-            HIP_CHECK(hipMemcpyAsync(d_desc, sorted.data(), sizeof(ChainDev) * (size_t)n, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-        }
-        int n_narrow = 0;
-        for (int i = 0; i < n; ++i) n_narrow += !geo[i].wide;
-        ranges[0] = Range{0, n_narrow, false};
-        ranges[1] = Range{n_narrow, n - n_narrow, true};
-
-        size_t pair_lds[2] = {0, 0};
-        long long max_pairs[2] = {0, 0};
-        for (int i = 0; i < n; ++i) {
-            int w = geo[i].wide;
-            const size_t no = (size_t)jobs[i].n_out, cellb = geo[i].wide ? 8 : 4;
-            const size_t s = align_up(sel2_fixed_lds(jobs[i].n_out, geo[i]) + (size_t)desc[i].claim_words * 4, 16);
-            if (s > sel2_lds_budget(im.device, geo[i].wide))
-                throw std::runtime_error("selection kernel needs " + std::to_string(s) + " bytes of dynamic LDS, the device leaves it " + std::to_string(sel2_lds_budget(im.device, geo[i].wide)) +
-                                         " beside the kernel's static arrays (n_out too large)");
-            sel_lds[w] = std::max(sel_lds[w], s);
-            upd_lds[w] = std::max(upd_lds[w], align_up(2 * no * cellb + no * 6, 16) + align_up((size_t)UPD_WAVES * (QN * 3 + 1) * (size_t)geo[i].Kpad * 4, 16));  // UpdLds: hand-off tables | counters
-            pair_lds[w] = std::max(pair_lds[w], (size_t)4 * geo[i].Kpad * 4);
-            max_pairs[w] = std::max(max_pairs[w], (long long)jobs[i].n_in * (jobs[i].n_in + 1) / 2);
-        }
-        for (int w = 0; w < 2; ++w) {
-            const Range &r = ranges[w];
-            if (r.count == 0) continue;
-            upd_blocks[w] = std::max(2, std::min(64, (im.upd_total_blocks + r.count - 1) / r.count));  // at least 2 and at most 64 blocks per chain
-            ChainDev *base = d_desc + r.first;
-            const dim3 colgrid((max_n_out + 3) / 4, r.count), pairgrid((unsigned)((max_pairs[w] + 3) / 4), r.count);
-            with_cell(r.wide, [&](auto c) {
-                hipLaunchKernelGGL(k_init_cells<decltype(c)>, colgrid, dim3(256), 0, st, base);
-                hipLaunchKernelGGL(k_init_pairs<decltype(c)>, pairgrid, dim3(256), pair_lds[w], st, base);
-            });
-            HIP_CHECK(hipGetLastError());
-        }
-        for (int w = 0; w < 2; ++w)
-            if (ranges[w].count) sel2_allow_lds<false>(ranges[w].wide, sel_lds[w]);
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-
-    // ---- 4. greedy loop: two kernels per iteration.  The chains are split into up to four groups, each advancing
-    // in lockstep on its own stream, so that the one-block-per-chain select kernel of one group overlaps the update
-    // kernel of the others.
-    // On an exception the helper thread is told to quit and joined, then the group streams and the poll stream are drained, then (with
-    // this object) the events are destroyed: the declaration order groups, drain, helper, join_helper below, after the member `events`.
-    void greedy_loop() {
-        ev0 = events.make(), ev1 = events.make();
-        HIP_CHECK(hipEventRecord(ev0, st));
-        HIP_CHECK(hipStreamSynchronize(st));  // set-up done before the group streams start
-        struct Group {
-            int first, count, w;  // descriptor range, cell width index
-            hipStream_t stream;
-        };
-        std::vector<Group> groups;
-        for (int w = 0; w < 2; ++w) {
-            const Range &r = ranges[w];
-            if (r.count == 0) continue;
-            int parts = std::max(1, std::min(im.n_lanes, r.count / 8));
-            if (ranges[0].count && ranges[1].count) parts = std::max(1, parts / 2);
-            for (int p = 0; p < parts; ++p) {
-                int lo = r.first + (int)((long long)r.count * p / parts), hi = r.first + (int)((long long)r.count * (p + 1) / parts);
-                groups.push_back(Group{lo, hi - lo, w, im.lanes[groups.size() % Impl::MAX_LANES]});
-            }
-        }
-        sampled_chains = groups.empty() ? 0 : groups[0].count;
-        // One greedy iteration of one group = (select, update) on the group's stream.
-        // `step` = the number of the lockstep iteration = the iteration count of every chain that has not finished (every launch pair advances
-        // each of them by one): a kernel argument, because the search block of the selection must not read a field its sibling writes
-        // DA4ML_HIP_STATS=1: k_iter_update tallies the blocks it finds / creates / deletes (da_timings' found / inserts, the "peak pair blocks" of da_result_stats);
-        // read at every call, so that a benchmark can count on one pass and time the others
-        const char *stats_env = std::getenv("DA4ML_HIP_STATS");
-        const bool with_stats = stats_env && std::atoi(stats_env) != 0;
-        auto launch_pair = [&](const Group &gr, hipEvent_t *se, int step) {
-            ChainDev *base = d_desc + gr.first;
-            const dim3 sel_grid((gr.count + 7) & ~7, 2);  // y = 0 search block, y = 1 substitution block
-            // (+ 2: the last two blocks of a chain write the six blocks of the pairs among the modified rows)
-            const dim3 upd_grid((gr.count + 7) & ~7, upd_blocks[gr.w] + 2);
-            with_cell(gr.w != 0, [&](auto c) {
-                using Cell = decltype(c);
-                if (se) HIP_CHECK(hipEventRecord(se[0], gr.stream));
-                hipLaunchKernelGGL(k_iter_select2<Cell>, sel_grid, dim3(SEL2_THREADS), sel_lds[gr.w], gr.stream, base, gr.count, im.d_done, step);
-                if (se) HIP_CHECK(hipEventRecord(se[1], gr.stream));
-                with_flag(with_stats, [&](auto s) {
-                    hipLaunchKernelGGL((k_iter_update<Cell, decltype(s)::value>), upd_grid, dim3(UPD_THREADS), upd_lds[gr.w], gr.stream, base, gr.count);
-                });
-                if (se) HIP_CHECK(hipEventRecord(se[2], gr.stream));
-            });
-        };
-        // Windows of up to WINDOW_ITERS iterations x all groups are queued eagerly; one event-bracketed iteration per window
-        // samples the kernel durations.  (A hipGraph replay of the window was re-measured in round 2: no gain.)
-        constexpr int WINDOW_ITERS = 63, MAX_SAMPLES = 4096;
-        long long iter_cap = 0;
-        int active = n;  // chains that have not finished: those with a method that takes no step never start
-        for (int i = 0; i < n; ++i) {
-            iter_cap = std::max<long long>(iter_cap, geo[i].rcap - jobs[i].n_in + 2);
-            active -= desc[i].done ? 1 : 0;
-        }
-        const int poll_every = WINDOW_ITERS + 1, pre_done = n - active;
-        // The done counter is read back ONE WINDOW BEHIND on a separate stream: after window w is queued, the poll stream
-        // waits for every group's end-of-window event and copies the counter; the host looks at the copy of window w-1 only
-        // after window w has been queued, so the queues never drain while the host decides whether to go on.
-        hipEvent_t win_ev[2][Impl::MAX_LANES], copy_ev[2];
-        for (int p = 0; p < 2; ++p) {
-            copy_ev[p] = events.make(hipEventDisableTiming);
-            for (size_t gi = 0; gi < groups.size(); ++gi) win_ev[p][gi] = events.make(hipEventDisableTiming);
-        }
-        im.h_done[0] = im.h_done[1] = 0;
-        long long window = 0;
-        struct DrainOnError {  // an exception between here and the end of the loop leaves launches queued: let them finish before the arena is reused
-            const std::vector<Group> &g;
-            hipStream_t poll;
-            bool armed = true;
-            ~DrainOnError() {
-                if (!armed) return;
-                for (const Group &gr : g) (void)hipStreamSynchronize(gr.stream);
-                (void)hipStreamSynchronize(poll);
-            }
-        } drain{groups, im.poll_stream};
-        // A second launching thread takes every other chain group: with the shorter kernels of round 5 one thread queueing all launches
-        // (2.85 us each, 8 per lockstep iteration of 4 groups) is the bound for small problems (64x64: 22.9 of 24.6 us per iteration, measured).
-        // It follows the windows of this thread: (first step, iterations) in, its groups' end-of-window events recorded out.
-        struct Helper {
-            std::atomic<long long> seq{0}, ack{0};
-            std::atomic<bool> quit{false};
-            long long first_step = 0;
-            int iters = 0, parity = 0;
-            std::exception_ptr err;
-            std::thread th;
-        } helper;
-        const bool two_threads = im.launch_threads >= 2 && groups.size() >= 2;
-        auto mine = [&](size_t gi, int who) { return !two_threads || (int)(gi & 1) == who; };
-        auto window_launches = [&](int who, long long first_step, int iters, int parity, hipEvent_t *se0) {
-            for (int it = 0; it < iters; ++it)
-                for (size_t gi = 0; gi < groups.size(); ++gi)
-                    if (mine(gi, who)) launch_pair(groups[gi], it == 0 && gi == 0 ? se0 : nullptr, (int)(first_step + it));
-            HIP_CHECK(hipGetLastError());
-            for (size_t gi = 0; gi < groups.size(); ++gi)
-                if (mine(gi, who)) HIP_CHECK(hipEventRecord(win_ev[parity][gi], groups[gi].stream));
-        };
-        if (two_threads)
-            helper.th = std::thread([&] {
-                long long seen = 0;
-                try {
-                    HIP_CHECK(hipSetDevice(im.device));
-                    while (true) {
-                        long long s;
-                        unsigned polls = 0;
-                        while ((s = helper.seq.load(std::memory_order_acquire)) == seen && !helper.quit.load(std::memory_order_acquire)) spin_wait_step(polls);
-                        if (s == seen) break;
-                        seen = s;
-                        if (!helper.err) window_launches(1, helper.first_step, helper.iters, helper.parity, nullptr);
-                        helper.ack.store(seen, std::memory_order_release);
-                    }
-                } catch (...) {
-                    helper.err = std::current_exception();
-                    helper.ack.store(helper.seq.load(), std::memory_order_release);  // (whatever window was being served: the main thread rethrows)
-                    unsigned polls = 0;
-                    while (!helper.quit.load(std::memory_order_acquire)) {  // keep acknowledging until told to leave
-                        helper.ack.store(helper.seq.load(), std::memory_order_release);
-                        spin_wait_step(polls);
-                    }
-                }
-            });
-        struct JoinHelper {
-            Helper &h;
-            ~JoinHelper() {
-                h.quit.store(true, std::memory_order_release);
-                if (h.th.joinable()) h.th.join();
-            }
-        } join_helper{helper};
-        while (active > 0) {
-            const auto t_q0 = std::chrono::steady_clock::now();
-            if (launched_iters > iter_cap + 2 * poll_every) throw std::runtime_error("greedy loop did not terminate within its row capacity (internal error)");
-            // small problems finish within a few iterations: start with short windows, double up to the full length
-            const int this_window = (int)std::min<long long>(WINDOW_ITERS, (8ll << std::min<long long>(window, 8)) - 1);
-            const int p = (int)(window & 1);
-            if (two_threads) {
-                helper.first_step = launched_iters, helper.iters = this_window + 1, helper.parity = p;
-                helper.seq.fetch_add(1, std::memory_order_release);
-            }
-            // the first iteration of a window is the sampled one: the first group's kernels are bracketed by events on its stream
-            hipEvent_t se[3];
-            const bool sample = sample_ev.size() < (size_t)3 * MAX_SAMPLES;
-            if (sample)
-                for (auto &e : se) {
-                    e = events.make();
-                    sample_ev.push_back(e);
-                }
-            window_launches(0, launched_iters, this_window + 1, p, sample ? se : nullptr);
-            launched_iters += this_window + 1;
-            if (two_threads) {
-                const long long want = helper.seq.load(std::memory_order_relaxed);
-                unsigned polls = 0;
-                while (helper.ack.load(std::memory_order_acquire) != want) spin_wait_step(polls);
-                if (helper.err) std::rethrow_exception(helper.err);
-            }
-            for (size_t gi = 0; gi < groups.size(); ++gi) HIP_CHECK(hipStreamWaitEvent(im.poll_stream, win_ev[p][gi], 0));
-            HIP_CHECK(hipMemcpyAsync(&im.h_done[p], im.d_done, sizeof(unsigned int), hipMemcpyDeviceToHost, im.poll_stream));
-            HIP_CHECK(hipEventRecord(copy_ev[p], im.poll_stream));
-            host_launch_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_q0).count();
-            if (window > 0) {
-                HIP_CHECK(hipEventSynchronize(copy_ev[p ^ 1]));
-                active = n - pre_done - (int)im.h_done[p ^ 1];
-            }
-            ++window;
-        }
-        for (const Group &gr : groups) HIP_CHECK(hipStreamSynchronize(gr.stream));
-        HIP_CHECK(hipStreamSynchronize(im.poll_stream));
-        drain.armed = false;
-        HIP_CHECK(hipEventRecord(ev1, st));
-    }
-
-    // ---- 5. extraction, the final descriptors and the loop's clocks; every outs[] reset to what its chain reports.  True: some chain outgrew its arena
-    bool extract() {
-        for (int w = 0; w < 2; ++w) {
-            const Range &r = ranges[w];
-            if (r.count == 0) continue;
-            const dim3 colgrid((max_n_out + 3) / 4, r.count);
-            with_cell(r.wide, [&](auto c) { hipLaunchKernelGGL(k_extract<decltype(c)>, colgrid, dim3(256), 0, st, d_desc + r.first); });
-        }
-        hipLaunchKernelGGL(k_pack, dim3(n), dim3(256), 0, st, d_desc);
-        HIP_CHECK(hipGetLastError());
-        fin.resize(n);
-        HIP_CHECK(hipMemcpyAsync(fin.data(), d_desc, sizeof(ChainDev) * (size_t)n, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipEventElapsedTime(&loop_ms, ev0, ev1));
-        const int n_samples = (int)(sample_ev.size() / 3);
-        for (int k = 0; k < n_samples; ++k) {
-            float a = 0, b = 0;
-            HIP_CHECK(hipEventElapsedTime(&a, sample_ev[3 * k], sample_ev[3 * k + 1]));
-            HIP_CHECK(hipEventElapsedTime(&b, sample_ev[3 * k + 1], sample_ev[3 * k + 2]));
-            im.timings.select_ms_sampled += a;
-            im.timings.update_ms_sampled += b;
-        }
-        im.timings.samples += n_samples;
-        im.timings.sampled_chain_launches += (double)n_samples * sampled_chains;
-        bool need_retry = false;
-        for (int s = 0; s < n; ++s) {
-            fill_result(outs[order[s]], fin[s]);
-            need_retry |= fin[s].error == E_TABLE_CAPACITY || fin[s].error == E_ROW_CAPACITY;
-        }
-        return need_retry;
-    }
-
-    // ---- 6. Results: the seven arrays of every chain (column offsets, shifts, picks, row latencies, surviving digits) are gathered
-    // into one contiguous device buffer by k_gather and leave in ONE copy into pinned memory (they used to leave one by one:
-    // 448 copies per 64-chain batch in two synchronised phases).
-    void download() {
-        struct ResultOffsets {
-            size_t st, s0, s1, pk, lat, row, cell;
-            uint32_t total;
-        };
-        std::vector<ResultOffsets> roff(n);
-        pieces.reserve((size_t)n * 7);
-        size_t gather_bytes = 0;
-        auto piece = [&](const void *src, size_t bytes) {
-            const size_t at = gather_bytes;
-            if (bytes) pieces.push_back(GatherPiece{src, (unsigned long long)at, (unsigned long long)bytes});
-            gather_bytes += align_up(bytes, 64);
-            return at;
-        };
-        for (int s = 0; s < n; ++s) {
-            const ChainDev &d = fin[s];
-            const ChainJob &j = jobs[order[s]];
-            ResultOffsets &ro = roff[s];
-            ro.total = d.error == E_OK ? d.pk_total : 0u;  // a failed chain delivers no digits (finalize_chain raises for it)
-            ro.st = piece(d.fin_start, ((size_t)j.n_out + 1) * 4);
-            ro.s0 = piece(d.shift0, (size_t)j.n_in);
-            ro.s1 = piece(d.shift1, (size_t)j.n_out);
-            ro.pk = piece(d.picks, (size_t)d.iter * sizeof(int4));
-            ro.lat = piece(d.pk_lat, (size_t)d.n_rows * 4);
-            ro.row = piece(d.pk_row, (size_t)ro.total * 4);
-            ro.cell = piece(d.pk_cell, (size_t)ro.total * 8);
-        }
-        unsigned char *pin = static_cast<unsigned char *>(im.pinned.get(std::max<size_t>(gather_bytes, 64)));
-        unsigned char *gbuf = static_cast<unsigned char *>(im.gather_buf.get(std::max<size_t>(gather_bytes, 64)));
-        GatherPiece *d_pieces = static_cast<GatherPiece *>(im.piece_buf.get(std::max<size_t>(pieces.size(), 1) * sizeof(GatherPiece)));
-        HIP_CHECK(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, st));
-        for (size_t first = 0; first < pieces.size(); first += 32768) {  // grid.y is a 16-bit quantity
-            const unsigned cnt = (unsigned)std::min<size_t>(32768, pieces.size() - first);
-            hipLaunchKernelGGL(k_gather, dim3(16, cnt), dim3(256), 0, st, d_pieces + first, gbuf);
-        }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(pin, gbuf, gather_bytes, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        // out of the pinned buffer into the result vectors: the chains on a few host threads (45 MB per 64-chain batch)
-        parallel_for(n, gather_bytes, [&](int s) {
-            const ChainDev &d = fin[s];
-            const ChainJob &j = jobs[order[s]];
-            const ResultOffsets &ro = roff[s];
-            ChainOut &o = outs[order[s]];
-            const uint32_t *cs = reinterpret_cast<const uint32_t *>(pin + ro.st);
-            o.col_start.assign(cs, cs + j.n_out + 1);
-            o.shift0.assign(reinterpret_cast<const int8_t *>(pin + ro.s0), reinterpret_cast<const int8_t *>(pin + ro.s0) + j.n_in);
-            o.shift1.assign(reinterpret_cast<const int8_t *>(pin + ro.s1), reinterpret_cast<const int8_t *>(pin + ro.s1) + j.n_out);
-            const int32_t *pk = reinterpret_cast<const int32_t *>(pin + ro.pk);
-            o.picks.assign(pk, pk + (size_t)d.iter * 4);
-            const float *lat = reinterpret_cast<const float *>(pin + ro.lat);
-            o.row_lat.assign(lat, lat + d.n_rows);
-            const uint32_t *pr = reinterpret_cast<const uint32_t *>(pin + ro.row);
-            const unsigned long long *pc = reinterpret_cast<const unsigned long long *>(pin + ro.cell);
-            o.dig_row.assign(pr, pr + ro.total);
-            o.dig_cell.assign(pc, pc + ro.total);
-        });
-    }
-
-    // ---- 7. the call into the backend's timings (a call that hands its chains to other calls -- halves, a retry -- does not get here)
-    void account() {
-        GpuTimings &tm = im.timings;
-        for (int s = 0; s < n; ++s) {
-            const ChainDev &d = fin[s];
-            for (int q = 0; q < 12; ++q) tm.phase_cycles[q] += (double)d.st_phase[q];
-            for (int q = 0; q < 4; ++q) tm.search_cycles[q] += (double)d.st_qphase[q];
-            tm.search_diag[0] += (double)d.st_qdiag[0], tm.search_diag[1] += (double)d.st_qdiag[1], tm.search_diag[2] += (double)d.st_qdiag[4];
-            tm.search_diag[3] += (double)d.st_qdiag[5], tm.search_diag[4] = std::max(tm.search_diag[4], (double)d.st_qdiag[6]), tm.search_diag[5] += (double)d.st_qdiag[7], tm.search_diag[6] += (double)d.st_qdiag[8];
-            tm.fast_steps += (long long)d.st_fast;
-            tm.found += (long long)d.st_found;
-            tm.inserts += (long long)d.st_inserts;
-            tm.cell_reads += (long long)d.st_cells;
-            tm.key_bytes += 2.0 * d.K * (double)(d.st_found + d.st_inserts);
-            tm.cell_bytes += (geo[order[s]].wide ? 8.0 : 4.0) * (double)d.st_cells;
-            tm.iterations += d.iter;
-            tm.rescans += (long long)d.st_rescans;
-            // + the search block: bound, flags, tie word and lowered-value mark of every group per step (28 B), and per re-read group its ranks and ~2 slots' key and index
-            tm.select_bytes += (double)d.st_sel_bytes + 32.0 * (double)d.n_groups * (double)d.iter + (double)d.st_rescans * ((double)(4u << d.gs_log2) + 24.0);
-            tm.partners += (long long)d.st_partners;
-            tm.table_bytes += (double)d.C * (8.0 + 4.0 + (double)(1 << d.pb_log2));
-        }
-        tm.loop_ms += loop_ms;
-        tm.host_launch_ms += host_launch_ms;
-        tm.lockstep_iters += launched_iters;
-        tm.chains += n;
-        tm.arena_bytes = std::max(tm.arena_bytes, (double)arena_bytes);
-    }
-};
-
-// Runs the chains of a batch to completion: the phases of Impl::Batch, and the two ways a call hands its chains on to other calls.
-void HipBackend::run_chains(const ChainJob *jobs, ChainOut *outs, int n) {
-    if (n <= 0) return;
-    Impl &im = *impl_;
-    HIP_CHECK(hipSetDevice(im.device));
-    auto t_begin = std::chrono::steady_clock::now();
-    const bool verbose = std::getenv("DA4ML_HIP_VERBOSE") != nullptr;
-    auto lap = [&, last = t_begin](const char *what) mutable {
-        auto now = std::chrono::steady_clock::now();
-        if (verbose) std::fprintf(stderr, "[da4ml_hip] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - last).count());
-        last = now;
-    };
-    Impl::Batch b(im, jobs, outs, n);
-    b.upload_and_prepare();
-    lap("upload + k_prepare");
-    b.plan(row_scale_);
-    // a batch whose arena does not fit into (most of) the free device memory is processed in two halves
-    if (b.arena_bytes > b.budget) {
-        if (n == 1)
-            throw std::runtime_error("a single chain needs " + std::to_string(b.arena_bytes >> 20) + " MiB of device memory (pair table of " +
-                                     std::to_string(b.geo[0].C) + " slots), " + std::to_string(b.free_b >> 20) + " MiB are free (budget " +
-                                     std::to_string(b.budget >> 20) + " MiB)");
-        const int half_n = n / 2;
-        run_chains(jobs, outs, half_n);
-        run_chains(jobs + half_n, outs + half_n, n - half_n);
-        return;
-    }
-    b.init_chains();
-    lap("arena + init kernels");
-    b.greedy_loop();
-    lap("greedy loop");
-    if (b.extract() && retry_depth_ < 4) {
-        // some chain outgrew its arena: rerun the whole group with larger capacities (rare; sizes are heuristics)
-        struct Restore {  // however the rerun ends
-            double &table_scale, &row_scale;
-            int &depth;
-            const double keep_t = table_scale, keep_r = row_scale;
-            ~Restore() {
-                table_scale = keep_t;
-                row_scale = keep_r;
-                --depth;
-            }
-        } restore{im.table_scale, row_scale_, retry_depth_};
-        ++retry_depth_;
-        im.timings.retries += 1;
-        im.table_scale *= 4.0;
-        row_scale_ *= 4.0;
-        run_chains(jobs, outs, n);
-        return;
-    }
-    b.download();
-    b.account();
-    lap("extract + download + unpack");
-    im.timings.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-}
-
-// ------------------------------------------------------------------------------------------------ column-sharded chain
-namespace {
-
-// da::ShardEngine on the GPU: one chain, the digits of the columns [c0, c1), a replica of the pair table.  Phases are
-// kernel launches on the backend's stream, each followed by a stream synchronisation: the exchange between the phases
-// (all-reduce of the buffers handed out here) is issued by the caller on its own stream / library.
-class HipShardEngine : public ShardEngine {
-  public:
-    HipShardEngine(hipStream_t st, int device, const ChainJob &job, int c0, int c1, double table_scale, double row_scale)
-        : st_(st), device_(device), job_(job), n_loc_(c1 - c0) {
-        HIP_CHECK(hipSetDevice(device_));
-        // inputs + centred matrix of the WHOLE matrix (centring and digit width are global properties)
-        const InputLayout L = input_layout(job.n_in, job.n_out);
-        unsigned char *io = static_cast<unsigned char *>(io_.get(L.bytes + 256));
-        fill_job(d_, job, n_loc_, c0, io, L);
-        HIP_CHECK(hipMemcpyAsync(io + L.kernel, job.kernel, (size_t)job.n_in * job.n_out * 4, hipMemcpyHostToDevice, st_));
-        HIP_CHECK(hipMemcpyAsync(io + L.qints, job.qints, (size_t)job.n_in * 12, hipMemcpyHostToDevice, st_));
-        HIP_CHECK(hipMemcpyAsync(io + L.lats, job.lats, (size_t)job.n_in * 4, hipMemcpyHostToDevice, st_));
-        dd_ = static_cast<ChainDev *>(desc_.get(sizeof(ChainDev)));
-        push();
-        hipLaunchKernelGGL(k_prepare, dim3(1), dim3(256), (size_t)job.n_out * 4, st_, dd_);
-        HIP_CHECK(hipGetLastError());
-        pull();
-        // geometry: the batch's, of n_loc_ columns, with the statistics of the whole matrix (the table is global)
-        static const GeometryErrors msg{"kernel needs more than 30 CSD digits per entry; unsupported", "problem too large for the row-reference format"};
-        if (job.adder_size >= 0 || job.carry_size >= 0) step_tab_.build(job.qints, job.n_in);  // -log2f of non-power-of-two input steps (StepLog2), as in run_chains
-        geo_ = derive_geometry(d_, job, n_loc_, (int)step_tab_.mant.size(), table_scale, row_scale, msg);
-        const Geometry &g = geo_;
-        n_pairs_ = (long long)job.n_in * (job.n_in + 1) / 2;
-        // arena: the chain's arrays (local column count) + the exchange buffers
-        ChainDev tmp;
-        const size_t chain_bytes = carve_chain(nullptr, n_loc_, g, tmp);
-        const size_t init_b = align_up((size_t)n_pairs_ * g.K * 4, 256), flag_b = align_up((((size_t)g.rcap + 3) / 4 + SHARD_TRAILER) * 4 + 64, 256),
-                     uni_b = align_up((size_t)g.rcap * 4, 256), slab_b = align_up((size_t)(6 + 3 * (size_t)g.rcap) * g.K * 4, 256);
-        const size_t need = chain_bytes + init_b + flag_b + uni_b + slab_b;
-        {
-            size_t free_b = 0, total_b = 0;
-            HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-            if (need > free_b)
-                throw std::runtime_error("a column-sharded chain needs " + std::to_string(need >> 20) + " MiB of device memory (pair table of " +
-                                         std::to_string(g.C) + " slots), " + std::to_string(free_b >> 20) + " MiB are free");
-        }
-        unsigned char *a = static_cast<unsigned char *>(arena_.get(need));
-        carve_chain(a, n_loc_, g, d_);
-        d_.cs_init = reinterpret_cast<int32_t *>(a + chain_bytes);
-        d_.cs_flags = reinterpret_cast<int32_t *>(a + chain_bytes + init_b);
-        d_.cs_uni = reinterpret_cast<uint32_t *>(a + chain_bytes + init_b + flag_b);
-        d_.cs_slab = reinterpret_cast<int32_t *>(a + chain_bytes + init_b + flag_b + uni_b);
-        apply_geometry(d_, g, sel2_lds_budget(device_, g.wide));
-        HIP_CHECK(hipMemsetAsync(d_.stamp, 0, sizeof(uint32_t) * (size_t)g.rcap, st_));
-        HIP_CHECK(hipMemsetAsync(d_.hkey, 0xFF, sizeof(unsigned long long) * (size_t)g.C, st_));
-        HIP_CHECK(hipMemsetAsync(d_.hrank, 0, sizeof(uint32_t) * (size_t)g.C, st_));
-        HIP_CHECK(hipMemsetAsync(d_.grec, 0, sizeof(GroupRec) * (size_t)g.n_groups, st_));  // (bound 0 = nothing in the group: its flag is not looked at; the first entry that rises sets it)
-        HIP_CHECK(hipMemsetAsync(d_.colbits, 0, sizeof(uint32_t) * (size_t)n_loc_ * d_.cb_words, st_));
-        upload_step_table(d_, step_tab_, st_);  // (step_tab_ is a member: alive until the synchronise below and beyond)
-        push();
-        report_ = static_cast<volatile int *>(report_buf_.get(64));
-        for (int q = 0; q < 5; ++q) report_[q] = 0;
-        d_done_ = static_cast<unsigned int *>(done_buf_.get(sizeof(unsigned int)));  // (a member buffer: released also when a later check of this constructor throws)
-        HIP_CHECK(hipMemsetAsync(d_done_, 0, sizeof(unsigned int), st_));
-        per_cell([&](auto c) { hipLaunchKernelGGL(k_init_cells<decltype(c)>, dim3((n_loc_ + 3) / 4, 1), dim3(256), 0, st_, dd_); });
-        HIP_CHECK(hipGetLastError());
-        sel_lds_ = align_up(sel2_fixed_lds(n_loc_, g) + (size_t)d_.claim_words * 4, 16);
-        if (sel_lds_ > sel2_lds_budget(device_, g.wide)) throw std::runtime_error("selection kernel needs more dynamic LDS than the device leaves beside its static arrays (n_out too large)");
-        sel2_allow_lds<true>(g.wide, sel_lds_);
-        part_lds_ = align_up(2 * (size_t)n_loc_ * (g.wide ? 8 : 4) + 4 * 3 * (size_t)g.Kpad * 4 + (size_t)n_loc_ * 2, 16);
-        HIP_CHECK(hipStreamSynchronize(st_));
-    }
-    ~HipShardEngine() override { (void)hipSetDevice(device_); }
-    bool on_device() const override { return true; }
-    int n_keys() const override { return geo_.K; }
-    int32_t *init_counts(int64_t &count) override {
-        const dim3 grid((unsigned)((n_pairs_ + 3) / 4));
-        per_cell([&](auto c) { hipLaunchKernelGGL(k_cs_init_counts<decltype(c)>, grid, dim3(256), (size_t)4 * geo_.Kpad * 4, st_, dd_); });
-        sync();
-        count = n_pairs_ * geo_.K;
-        return d_.cs_init;
-    }
-    void init_table() override {
-        const dim3 grid((unsigned)((n_pairs_ + 3) / 4));
-        per_cell([&](auto c) { hipLaunchKernelGGL(k_cs_init_table<decltype(c)>, grid, dim3(256), 0, st_, dd_); });
-        HIP_CHECK(hipGetLastError());
-    }
-    void set_stream_ordered(bool on) override { stream_ordered_ = on; }
-    // The host reads NOTHING back between the kernels of a step except, once per step, the summed status trailer and the size
-    // of the partner union (one synchronisation): the rows before a step are n_in + the steps taken, and a chain that stops
-    // writes its zero flags and trailer on the device (select_body, shard_stop).  With a stream-ordered transport (the library's
-    // RCCL transport: collectives queued on this stream) that is the only synchronisation of a step; a callback transport is
-    // handed completed buffers, i.e. one synchronisation in front of each of its two calls.
-    void select(int32_t *&flags, int64_t &fcount) override {
-        fw_ = flag_words(job_.n_in + (int)steps_);  // rows before this step
-        if (!stopped_) {
-            // the two-block selection of the ordinary chains (search beside substitution, the pick known one step ahead): the table is a replica,
-            // so every rank takes the same pick; the substitution block leaves flags and partial special-pair counts instead of a partner list
-            per_cell([&](auto c) { hipLaunchKernelGGL((k_iter_select2<decltype(c), true>), dim3(1, 2), dim3(SEL2_THREADS), sel_lds_, st_, dd_, 1, d_done_, (int)steps_); });
-            HIP_CHECK(hipGetLastError());
-        } else {  // (not reached by ShardedBackend, which leaves the loop with the step that stopped; kept well-defined)
-            static const int32_t tr[SHARD_TRAILER] = {1, 0, 0};  // (static: read by an asynchronous copy)
-            HIP_CHECK(hipMemsetAsync(d_.cs_flags, 0, (size_t)fw_ * 4, st_));
-            HIP_CHECK(hipMemcpyAsync(d_.cs_flags + fw_, tr, sizeof tr, hipMemcpyHostToDevice, st_));
-            sync();
-        }
-        if (!stream_ordered_) sync();
-        flags = d_.cs_flags;
-        fcount = fw_ + SHARD_TRAILER;
-    }
-    int32_t *partial(int64_t &scount, int32_t status[SHARD_TRAILER]) override {
-        // the summed status and the size of the union come from the device itself: k_cs_union writes them into pinned host memory, the
-        // host waits for the step's sequence number -- no copies, no stream synchronisation (the launch is checked; a device fault
-        // surfaces through the bounded wait's fall-back synchronisation)
-        const int seq = ++report_seq_;
-        hipLaunchKernelGGL(k_cs_union, dim3(1), dim3(1024), 0, st_, dd_, report_, seq, (int)fw_);  // (on summed flags that are all zero when every rank has stopped: an empty union)
-        HIP_CHECK(hipGetLastError());
-        {
-            unsigned polls = 0, tries = 0;
-            while (__atomic_load_n(&report_[0], __ATOMIC_ACQUIRE) != seq) {
-                if (++tries > (1u << 16)) {  // (seconds of polling, most of it asleep) let the runtime wait -- and report a fault, if that is what it is
-                    sync();
-                    if (__atomic_load_n(&report_[0], __ATOMIC_ACQUIRE) != seq) throw std::runtime_error("column-sharded chain: the device did not report the step's status");
-                    break;
-                }
-                spin_wait_step(polls);
-            }
-        }
-        const int nuni = report_[1];
-        for (int q = 0; q < SHARD_TRAILER; ++q) trailer_[q] = report_[2 + q];
-        for (int q = 0; q < SHARD_TRAILER; ++q) status[q] = trailer_[q];
-        scount = 0;
-        if (status[0] != 0) {
-            stopped_ = true;
-            return nullptr;
-        }
-        nuni_ = nuni;
-        if (nuni > 0) {
-            const dim3 grid((unsigned)((nuni + 3) / 4));
-            per_cell([&](auto c) { hipLaunchKernelGGL(k_cs_partial<decltype(c)>, grid, dim3(256), part_lds_, st_, dd_); });
-        }
-        if (!stream_ordered_) sync();
-        scount = (int64_t)(6 + 3 * (int64_t)nuni) * geo_.K;
-        return d_.cs_slab;
-    }
-    void apply() override {
-        const dim3 grid((unsigned)((nuni_ + 6 + 3) / 4));
-        per_cell([&](auto c) { hipLaunchKernelGGL(k_cs_apply<decltype(c)>, grid, dim3(256), 0, st_, dd_); });
-        HIP_CHECK(hipGetLastError());
-        ++steps_;
-    }
-    void finish(ChainOut &o) override {
-        per_cell([&](auto c) { hipLaunchKernelGGL(k_extract<decltype(c)>, dim3((n_loc_ + 3) / 4, 1), dim3(256), 0, st_, dd_); });
-        hipLaunchKernelGGL(k_pack, dim3(1), dim3(256), 0, st_, dd_);
-        pull();
-        fill_result(o, d_);
-        const size_t iters = (size_t)d_.iter;
-        o.shift0.resize(job_.n_in);
-        o.shift1.resize(job_.n_out);
-        o.picks.resize(iters * 4);
-        o.row_lat.resize((size_t)d_.n_rows);
-        o.col_start.resize((size_t)n_loc_ + 1);
-        HIP_CHECK(hipMemcpyAsync(o.shift0.data(), d_.shift0, job_.n_in, hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipMemcpyAsync(o.shift1.data(), d_.shift1, job_.n_out, hipMemcpyDeviceToHost, st_));
-        if (iters) HIP_CHECK(hipMemcpyAsync(o.picks.data(), d_.picks, iters * sizeof(int4), hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipMemcpyAsync(o.row_lat.data(), d_.pk_lat, (size_t)d_.n_rows * 4, hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipMemcpyAsync(o.col_start.data(), d_.fin_start, ((size_t)n_loc_ + 1) * 4, hipMemcpyDeviceToHost, st_));
-        sync();
-        const size_t total = o.col_start[n_loc_];
-        o.dig_row.resize(total);
-        std::vector<unsigned long long> cells(total);
-        if (total) {
-            HIP_CHECK(hipMemcpyAsync(o.dig_row.data(), d_.pk_row, total * 4, hipMemcpyDeviceToHost, st_));
-            HIP_CHECK(hipMemcpyAsync(cells.data(), d_.pk_cell, total * 8, hipMemcpyDeviceToHost, st_));
-            sync();
-        }
-        o.dig_cell.assign(cells.begin(), cells.end());
-    }
-
-  private:
-    template <class F> void per_cell(F &&f) { with_cell(geo_.wide, f); }  // f(Cell{}) for this chain's cell type
-    void sync() {
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(st_));
-    }
-    void push() { HIP_CHECK(hipMemcpyAsync(dd_, &d_, sizeof d_, hipMemcpyHostToDevice, st_)); }
-    void pull() {
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(&d_, dd_, sizeof d_, hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-    }
-    hipStream_t st_;
-    StepLog2Host step_tab_;
-    int64_t fw_ = 0;                      // flag words of the current step (the status trailer follows them)
-    long long steps_ = 0;                 // greedy steps applied so far (rows = n_in + steps_)
-    bool stopped_ = false, stream_ordered_ = false;
-    int32_t trailer_[SHARD_TRAILER] = {0, 0, 0};
-    int device_;
-    ChainJob job_;
-    int n_loc_;  // columns of this rank (the first of them is d_.col0)
-    ChainDev d_;
-    ChainDev *dd_ = nullptr;
-    Geometry geo_;
-    DeviceBuffer io_, desc_, arena_;
-    DeviceBuffer done_buf_;
-    unsigned int *d_done_ = nullptr;
-    PinnedBuffer report_buf_;          // {sequence number, union size, status[3]} written by k_cs_union (mapped pinned memory)
-    volatile int *report_ = nullptr;
-    int report_seq_ = 0;
-    long long n_pairs_ = 0;
-    int nuni_ = 0;
-    size_t sel_lds_ = 0, part_lds_ = 0;
-};
-
-}  // namespace
-
-std::unique_ptr<ShardEngine> HipBackend::make_shard_engine(const ChainJob &job, int c0, int c1, double capacity_scale) {
-    return std::unique_ptr<ShardEngine>(new HipShardEngine(impl_->stream, impl_->device, job, c0, c1, impl_->table_scale * capacity_scale, row_scale_ * capacity_scale));
-}
-
-void HipBackend::column_distances(const int32_t *aug, int n_in, int W, int64_t *d0, int64_t *d1) {
-    Impl &im = *impl_;
-    HIP_CHECK(hipSetDevice(im.device));
-    hipStream_t st = im.stream;
-    size_t a_bytes = align_up((size_t)n_in * W * 4, 256), d_bytes = align_up((size_t)W * W * 8, 256);
-    unsigned char *buf = static_cast<unsigned char *>(im.io_buf.get(a_bytes + 2 * d_bytes));
-    HIP_CHECK(hipMemcpyAsync(buf, aug, (size_t)n_in * W * 4, hipMemcpyHostToDevice, st));
-    auto *dd0 = reinterpret_cast<long long *>(buf + a_bytes), *dd1 = reinterpret_cast<long long *>(buf + a_bytes + d_bytes);
-    EventGuard events;
-    hipEvent_t e0 = events.make(), e1 = events.make();
-    HIP_CHECK(hipEventRecord(e0, st));
-    hipLaunchKernelGGL(k_col_dist, dim3((W + 15) / 16, (W + 15) / 16), dim3(16, 16), 0, st, reinterpret_cast<const int32_t *>(buf), n_in, W, dd0, dd1);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(e1, st));
-    HIP_CHECK(hipMemcpyAsync(d0, dd0, (size_t)W * W * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(d1, dd1, (size_t)W * W * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    im.timings.dist_ms += ms;
-    im.timings.dist_calls += 1;
-}
-
-int HipBackend::int_to_csd(const int32_t *x, int64_t n, std::vector<int8_t> &csd) {
-    Impl &im = *impl_;
-    HIP_CHECK(hipSetDevice(im.device));
-    hipStream_t st = im.stream;
-    size_t xb = align_up(std::max<size_t>((size_t)n * 4, 4), 256);
-    // two-step: global |max| -> N, then the digits
-    unsigned char *buf = static_cast<unsigned char *>(im.io_buf.get(xb + 256 + (size_t)n * 33));
-    auto *dx = reinterpret_cast<int32_t *>(buf);
-    auto *dmax = reinterpret_cast<unsigned int *>(buf + xb);
-    auto *dout = reinterpret_cast<int8_t *>(buf + xb + 256);
-    HIP_CHECK(hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(dmax, 0, 4, st));
-    unsigned int mx = 0;
-    if (n > 0) {
-        int blocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
-        hipLaunchKernelGGL(k_absmax, dim3(blocks), dim3(256), 0, st, dx, (long long)n, dmax);
-        HIP_CHECK(hipMemcpyAsync(&mx, dmax, 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-    int N = csd_width(mx);
-    csd.assign((size_t)n * N, 0);
-    if (n > 0) {
-        hipLaunchKernelGGL(k_naf_digits, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx, (long long)n, N, dout);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(csd.data(), dout, (size_t)n * N, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-    return N;
-}
-
-int HipBackend::csd_decompose(const float *kernel, int n_in, int n_out, bool center, std::vector<int8_t> &csd,
-                              std::vector<int8_t> &s0, std::vector<int8_t> &s1) {
-    // centring on the device through k_prepare of a one-chain batch, then the digit kernel
-    Impl &im = *impl_;
-    HIP_CHECK(hipSetDevice(im.device));
-    hipStream_t st = im.stream;
-    size_t e = (size_t)n_in * n_out;
-    std::vector<int32_t> xi(e);
-    if (center) {
-        const InputLayout L = input_layout(n_in, n_out, false);  // (no latencies: k_prepare does not read them)
-        unsigned char *buf = static_cast<unsigned char *>(im.io_buf.get(L.bytes + 512));
-        ChainDev d;
-        std::memset(&d, 0, sizeof d);
-        d.n_in = n_in;
-        d.n_out = n_out;
-        d.pn_out = n_out;
-        d.kernel = reinterpret_cast<const float *>(buf + L.kernel);
-        d.qints = reinterpret_cast<const float *>(buf + L.qints);
-        d.xint = reinterpret_cast<int32_t *>(buf + L.xint);
-        d.shift0 = reinterpret_cast<int8_t *>(buf + L.shift0);
-        d.shift1 = reinterpret_cast<int8_t *>(buf + L.shift1);
-        std::vector<float> ones((size_t)n_in * 3, 1.0f);  // no row is treated as dead here
-        HIP_CHECK(hipMemcpyAsync(buf + L.kernel, kernel, e * 4, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(buf + L.qints, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, st));
-        ChainDev *dd = static_cast<ChainDev *>(im.desc_buf.get(sizeof(ChainDev)));
-        HIP_CHECK(hipMemcpyAsync(dd, &d, sizeof d, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_prepare, dim3(1), dim3(256), (size_t)n_out * 4, st, dd);
-        HIP_CHECK(hipGetLastError());
-        s0.resize(n_in);
-        s1.resize(n_out);
-        HIP_CHECK(hipMemcpyAsync(xi.data(), d.xint, e * 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(s0.data(), d.shift0, n_in, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(s1.data(), d.shift1, n_out, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    } else {
-        s0.assign(n_in, 0);
-        s1.assign(n_out, 0);
-        for (size_t k = 0; k < e; ++k) xi[k] = (int32_t)kernel[k];
-    }
-    return int_to_csd(xi.data(), (int64_t)e, csd);
-}
-
-int device_count() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
+// in headers by concern, in dependency order; DA_ENGINE_TU lets them compile here and nowhere else
+#define DA_ENGINE_TU
+#include "hip_host_util.h"
+#include "hip_chain_setup.h"
+#include "hip_batch.h"
+#include "hip_shard_engine.h"
+#include "hip_stage01.h"
 
 }  // namespace gpu
 }  // namespace da

@@ -1,5 +1,5 @@
 // cmvm_geometry.h -- size of a greedy chain's row arena and pair-count table.  Plain C++, shared by
-// HipBackend::run_chains and the column-sharded chain (cmvm_engine.hip) and by the CPU tests (tests/geometry).
+// HipBackend::run_chains and the column-sharded chain (derive_geometry, hip_chain_setup.h) and by the CPU tests (tests/geometry).
 #pragma once
 
 #include <algorithm>

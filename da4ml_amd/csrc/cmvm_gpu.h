@@ -1,4 +1,4 @@
-// cmvm_gpu.h -- the HIP implementation of da::Backend (kernels in cmvm_engine.hip).
+// cmvm_gpu.h -- the HIP implementation of da::Backend (kernels in cmvm_engine.hip, host code in the hip_*.h headers it includes).
 #pragma once
 
 #include <memory>

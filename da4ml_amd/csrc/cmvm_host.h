@@ -3,6 +3,7 @@
 // Split of work:
 //   device (cmvm_engine.hip)   centring + CSD recoding, pair-count table, the greedy selection /
 //                              substitution / recount loop, stage-1 column distance matrix
+//                              (launched by the HIP backend: hip_*.h, parts of that translation unit)
 //   host   (this file)         option resolution, stage-1 minimum spanning tree and m0/m1 assembly,
 //                              per-output adder trees, op records (interval / latency / cost with the
 //                              host libm), candidate search and arg-min
