@@ -121,3 +121,107 @@ def _method_grid():
 
 
 METHOD_GRID = _method_grid()
+
+
+# ---- structured matrices: what quantised layer weights look like (ties across the whole pair table, duplicate rows / columns, sparsity) ----
+# name -> (medium shape: the GPU size, small twin: the emulated device's size)
+_STRUCTURED_SHAPES = {
+    'ones': ((64, 64), (12, 12)),
+    'ones_wide': ((8, 300), (4, 260)),  # more than 256 columns: wide layout, every column substituted in every step
+    'full85': ((48, 48), (12, 12)),
+    'full85_signs': ((48, 48), (12, 12)),
+    'full_m128': ((24, 20), (12, 10)),
+    'full_127': ((24, 20), (12, 10)),
+    'full_0x555': ((12, 12), (6, 6)),
+    'full_8191': ((12, 12), (6, 6)),
+    'frac85': ((24, 24), (12, 12)),
+    'diag': ((48, 48), (12, 12)),
+    'rank1': ((64, 64), (12, 12)),
+    'dup_rows': ((64, 48), (12, 12)),
+    'dup_cols': ((48, 64), (12, 12)),
+    'neg_cols': ((48, 48), (12, 12)),
+    'ternary_sparse': ((128, 128), (16, 16)),
+    'ternary_dense': ((64, 64), (12, 12)),
+    'pow2': ((64, 64), (12, 12)),
+    'toeplitz': ((64, 64), (12, 12)),
+    'checker_zero': ((32, 32), (12, 12)),
+    'one_hot_rows': ((40, 16), (12, 8)),
+}
+STRUCTURED = tuple(_STRUCTURED_SHAPES)
+
+SINGLE_CHAIN = dict(method0='wmc', method1='wmc', decompose_dc=-1, search_all_decompose_dc=False)
+# the option sets every structured family is recorded under (tests/golden/structured_golden.json.gz)
+STRUCTURED_OPTS = {
+    'single': SINGLE_CHAIN,
+    'default': {},
+    'mc_latency': dict(method0='mc', method1='mc-pdc', adder_size=1, carry_size=-1),
+    'wmc_dc_hard0': dict(method0='wmc-dc', method1='auto', hard_dc=0, adder_size=4, carry_size=8),
+    'mc_dc_hard2': dict(method0='mc-dc', method1='wmc-pdc', decompose_dc=0, hard_dc=2, search_all_decompose_dc=False),
+}
+
+
+def structured_matrix(name, small=False, shape=None):
+    """One matrix of a structured family: seeded, float32, C-contiguous.  `small`: the twin for the emulated device;
+    `shape`: any other size of the same construction (the seed depends on the family only)."""
+    n_in, n_out = shape or _STRUCTURED_SHAPES[name][1 if small else 0]
+    rng = np.random.default_rng(70_000 + STRUCTURED.index(name))
+    i, j = np.indices((n_in, n_out))
+    if name in ('ones', 'ones_wide'):
+        k = np.ones((n_in, n_out))
+    elif name == 'full85':  # 0b1010101: chained occurrences of one row pair at shifts 2, 4 and 6 that share digits
+        k = np.full((n_in, n_out), 85.0)
+    elif name == 'full85_signs':
+        k = 85.0 * (1 - 2 * ((i + j) % 2))
+    elif name == 'full_m128':
+        k = np.full((n_in, n_out), -128.0)
+    elif name == 'full_127':
+        k = np.full((n_in, n_out), 127.0)
+    elif name == 'full_0x555':  # 11 overlapping digits, narrow layout
+        k = np.full((n_in, n_out), float(0x555))
+    elif name == 'full_8191':  # digit 13: wide layout
+        k = np.full((n_in, n_out), 8191.0)
+    elif name == 'frac85':
+        k = np.full((n_in, n_out), 85.0 / 64.0)
+    elif name == 'diag':
+        k = 37.0 * (i == j)
+    elif name == 'rank1':
+        k = np.outer(rng.integers(-8, 8, n_in), rng.integers(-8, 8, n_out))
+    elif name == 'dup_rows':
+        assert n_in % 4 == 0
+        k = np.tile(rng.integers(-64, 64, (4, n_out)), (n_in // 4, 1))
+    elif name == 'dup_cols':
+        assert n_out % 4 == 0
+        k = np.tile(rng.integers(-64, 64, (n_in, 4)), (1, n_out // 4))
+    elif name == 'neg_cols':
+        assert n_out % 3 == 0
+        a = rng.integers(-64, 64, (n_in, n_out // 3))
+        k = np.concatenate([a, -a, 2 * a], axis=1)
+    elif name == 'ternary_sparse':
+        k = rng.choice([-1, 0, 1], size=(n_in, n_out), p=[0.05, 0.9, 0.05])
+    elif name == 'ternary_dense':
+        k = rng.choice([-1, 1], size=(n_in, n_out))
+    elif name == 'pow2':  # one digit per cell: no pair inside a cell, all pairs across rows
+        k = rng.choice([-1, 1], size=(n_in, n_out)) * 2.0 ** rng.integers(0, 7, (n_in, n_out))
+    elif name == 'toeplitz':
+        k = 21.0 * (((i - j) % 7) - 3)
+    elif name == 'checker_zero':
+        k = 51.0 * ((i + j) % 2 == 0)
+    elif name == 'one_hot_rows':
+        v = rng.integers(1, 64, n_in) * rng.choice([-1, 1], size=n_in)
+        k = np.zeros((n_in, n_out))
+        k[np.arange(n_in), rng.integers(0, n_out, n_in)] = v
+    else:
+        raise KeyError(name)
+    return np.ascontiguousarray(k + 0.0, dtype=np.float32)
+
+
+def samples_inside(stage, rng, n):
+    """n sample vectors on the grid of a stage's declared input intervals: the executor multiplies input i by 2^inp_shifts[i] and
+    wraps the product into the format of the input op's interval, so the samples are drawn in that frame and shifted back"""
+    cols = []
+    for q, sh in zip(stage.inp_qint, stage.inp_shifts):
+        if q.min == q.max == 0:  # an input nothing reads (a zero row; a zero column of stage 0): interval [0, 0], step inf
+            cols.append(np.zeros(n))
+            continue
+        cols.append(rng.integers(round(q.min / q.step), round(q.max / q.step) + 1, n) * q.step * 2.0**-sh)
+    return np.stack(cols, axis=1).astype(np.float64)

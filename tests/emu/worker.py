@@ -12,7 +12,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / 'tests'))
 
 import numpy as np  # noqa: E402
-from cases import int_matrix, random_case  # noqa: E402
+from cases import STRUCTURED, STRUCTURED_OPTS, int_matrix, random_case, structured_matrix  # noqa: E402
 
 from da4ml_amd import _binary as hip  # noqa: E402
 from oracle.oracle import Oracle  # noqa: E402
@@ -69,6 +69,24 @@ def layouts():
     }
     bad = [name for name, (k, opts) in cases.items() if hip.solve(k, **opts) != o.solve(k, **opts)]
     out(bad=bad, n=len(cases))
+
+
+EMU_STRUCTURED_ALL_OPTS = ('ones', 'full85', 'neg_cols', 'ternary_dense')  # the families that run under all five option sets here
+
+
+def structured(part, parts):
+    """the small twins of the structured families (cases.structured_matrix(name, small=True)): all of them as a single chain and
+    under the default search, four of them under the three other option sets too; this process takes every `parts`-th combination"""
+    o = Oracle('port')
+    todo = [(name, oname) for name in STRUCTURED for oname in STRUCTURED_OPTS if oname in ('single', 'default') or name in EMU_STRUCTURED_ALL_OPTS]
+    mine = todo[part::parts]
+    bad = []
+    for name, oname in mine:
+        k, opts = structured_matrix(name, small=True), STRUCTURED_OPTS[oname]
+        got = hip.solve(k, **opts)
+        if got != o.solve(k, **opts) or not np.all(got.kernel == k):
+            bad.append(f'{name}/{oname}')
+    out(bad=bad, n=len(mine), total=len(todo))
 
 
 def batch():
@@ -278,5 +296,5 @@ def dais():
 
 if __name__ == '__main__':
     what = sys.argv[1]
-    {'random': lambda: random_cases(int(sys.argv[2]), int(sys.argv[3])), 'oddsteps': lambda: odd_steps(int(sys.argv[2]), int(sys.argv[3])), 'layouts': layouts, 'batch': batch, 'lds_budget': lds_budget, 'retry': retry, 'big_table': big_table, 'sub_batch': sub_batch, 'fork': fork_after_use, 'record': lambda: record(sys.argv[2], sys.argv[3]),
+    {'random': lambda: random_cases(int(sys.argv[2]), int(sys.argv[3])), 'oddsteps': lambda: odd_steps(int(sys.argv[2]), int(sys.argv[3])), 'layouts': layouts, 'structured': lambda: structured(int(sys.argv[2]), int(sys.argv[3])), 'batch': batch, 'lds_budget': lds_budget, 'retry': retry, 'big_table': big_table, 'sub_batch': sub_batch, 'fork': fork_after_use, 'record': lambda: record(sys.argv[2], sys.argv[3]),
      'shard_single': shard_single, 'shard_retry': shard_retry, 'shard_rank': shard_rank, 'dais': dais, 'race_cases': race_cases}[what]()  # fmt: skip

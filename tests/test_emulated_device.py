@@ -52,6 +52,22 @@ def test_entry_layouts_and_their_boundaries(emu):
     assert emu('layouts')['bad'] == []
 
 
+def test_structured_matrices_small_twins(emu):
+    """the structured families of cases.STRUCTURED (all-ones, one value in every cell, duplicate / negated / doubled rows and columns,
+    ternary, rank 1, Toeplitz, zero checkerboards, one-hot rows) at their small sizes (about 12x12; 4x260 for the wide all-ones)
+    against the restatement: every family as a single chain and under the default search, `ones`, `full85`, `neg_cols` and
+    `ternary_dense` under the three other option sets as well -- 52 solves in two worker processes.  Left to the GPU suite
+    (tests/test_structured_gpu.py, which runs every family under all five sets at the medium sizes): the 16 other families under
+    mc / mc-pdc with the latency model, wmc-dc with hard_dc=0 and mc-dc with decompose_dc=0, hard_dc=2; and everything that
+    needs more than one table group, chunked substitution or concurrent wavefronts."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(2) as pool:
+        res = list(pool.map(lambda part: emu('structured', part, 2), range(2)))
+    assert [r['bad'] for r in res] == [[], []]
+    assert sum(r['n'] for r in res) == res[0]['total'] == 52
+
+
 def test_batched_chains(emu):
     r = emu('batch')
     assert r['bad'] == [] and r['chains'] >= 13

@@ -9,7 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from cases import int_matrix
+from cases import STRUCTURED, int_matrix, structured_matrix
 
 GEO_DIR = Path(__file__).resolve().parent / 'geometry'
 MAX_GROUPS = 2048  # DA_MAX_GROUPS of the product build
@@ -17,8 +17,7 @@ M_WMC, M_DUMMY = 3, 6
 LOAD_FACTOR = 0.5  # 1 / TABLE_SLOTS_PER_PAIR
 
 
-@pytest.fixture(scope='module')
-def geo():
+def load_geo():
     subprocess.run(['make', '-s', '-C', str(GEO_DIR)], check=True)
     lib = C.CDLL(str(GEO_DIR / 'libgeometry.so'))
     lib.geo_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_double, C.c_double, C.c_int, np.ctypeslib.ndpointer(np.int64)]
@@ -29,6 +28,11 @@ def geo():
         return dict(C=int(out[0]), gs_log2=int(out[1]), n_groups=int(out[2]), rcap=int(out[3]))
 
     return run
+
+
+@pytest.fixture(scope='module')
+def geo():
+    return load_geo()
 
 
 def naf_weight(x):
@@ -160,3 +164,67 @@ def test_capped_tables_hold_the_model_peak(geo, model, shape):
     capped = geo(n_in, n_out, pairs, digits, table_scale=1e4)
     assert heuristic_want(n_in, pairs, 1e4) > 1 << 25 and capped['C'] < heuristic_want(n_in, pairs, 1e4)
     assert capped['rcap'] > n_in + iterations  # (no row-capacity retry)
+
+
+def structured_prep(name):
+    """prep of a structured family at its medium size (frac85: scaled to integers by a power of two, which leaves the digits as they are)"""
+    k = structured_matrix(name)
+    while np.any(k != np.round(k)):
+        k = k * 2
+    return k, *prep(k)
+
+
+@pytest.mark.parametrize('name', STRUCTURED)
+def test_structured_families_get_a_geometry(geo, name):
+    """the pair statistics of the structured matrices sit at the extremes of the sizing rule (all-ones: every row pair in every column;
+    one-hot rows and the diagonal: no pair across rows at all) -- each gets a power-of-two table in at most 2048 groups"""
+    k, pairs, digits = structured_prep(name)
+    n_in, n_out = k.shape
+    if name in ('ones', 'ones_wide'):
+        assert pairs == n_out * (n_in * (n_in - 1) // 2) and digits == n_in * n_out
+    if name in ('diag', 'one_hot_rows'):
+        assert digits == int(naf_weight(k).sum()) and pairs == sum(w * (w - 1) // 2 for w in naf_weight(k).sum(axis=0))
+    for ts in (1.0, 4.0, 16.0):  # as sized, and after one and two capacity retries
+        g = geo(n_in, n_out, pairs, digits, table_scale=ts, row_scale=ts)
+        assert g['C'] >= 256 and g['C'] & (g['C'] - 1) == 0, (ts, g)
+        assert 1 <= g['n_groups'] <= MAX_GROUPS and g['C'] == g['n_groups'] << g['gs_log2'] and g['gs_log2'] >= 8, (ts, g)
+        assert g['rcap'] > n_in
+
+
+@pytest.mark.parametrize('name', ['ones', 'full85', 'dup_rows', 'ternary_dense'])
+def test_structured_tables_hold_the_model_peak(geo, model, name):
+    """the sequential engine model's exact peak of live blocks of a single wmc chain, over the load factor, fits the table the
+    chain gets without a capacity retry -- at the all-ones extreme of the pair count and on duplicate rows as on random matrices"""
+    k, pairs, digits = structured_prep(name)
+    n_in, n_out = k.shape
+    lib = model.lib
+    lib.mdl_stats.argtypes = [C.c_void_p, np.ctypeslib.ndpointer(np.int64)]
+    h = model.g('solve')(k, n_in, n_out, b'wmc', b'wmc', -1, -1, None, None, -1, -1, 0)
+    assert h, model.g('last_error')().decode()
+    st = np.zeros(8, np.int64)
+    lib.mdl_stats(h, st)
+    model.g('free')(h)
+    peak, iterations = int(st[4]), int(st[0])
+    g = geo(n_in, n_out, pairs, digits)
+    print(f'{name}: pairs {pairs} digits {digits} peak {peak} iterations {iterations} geometry {g}')
+    assert peak > 0 and iterations > 0
+    assert g['C'] >= peak / LOAD_FACTOR
+
+
+def scale_for_groups(geo, name, groups):
+    """the smallest power-of-two DA4ML_HIP_TABLE_SCALE at which the single chain of a structured family gets `groups` table groups"""
+    k, pairs, digits = structured_prep(name)
+    for e in range(0, 16):
+        if geo(*k.shape, pairs, digits, table_scale=float(2**e))['n_groups'] == groups:
+            return float(2**e)
+    raise AssertionError(f'no table scale gives {name} {groups} groups')
+
+
+def test_table_scale_forces_all_groups_on_the_tied_families(geo):
+    """tests/test_structured_gpu.py solves `ones` and `full85` with the scale found here: 2048 groups of 256 slots, every group bound of
+    the selection's arg-max in use, where the chains get 128 and 64 groups as sized"""
+    for name, groups, scale in (('ones', 128, 16.0), ('full85', 64, 32.0)):
+        k, pairs, digits = structured_prep(name)
+        assert geo(*k.shape, pairs, digits)['n_groups'] == groups
+        assert scale_for_groups(geo, name, MAX_GROUPS) == scale
+        assert strip(geo(*k.shape, pairs, digits, table_scale=scale)) == dict(C=1 << 19, gs_log2=8, n_groups=MAX_GROUPS)

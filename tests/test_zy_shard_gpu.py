@@ -35,6 +35,24 @@ for k, kw in cases:
 print(json.dumps({"same": same, "chains": chains}), flush=True)
 '''
 
+STRUCTURED_SINGLE = r'''
+import os, sys, json
+os.environ["DA4ML_SHARD_FORCE"] = "1"
+sys.path.insert(0, os.environ["DA_ROOT"]); sys.path.insert(0, os.path.join(os.environ["DA_ROOT"], "tests"))
+from da4ml_amd import _binary as hip
+from oracle.oracle import Oracle
+from cases import SINGLE_CHAIN, structured_matrix
+O = Oracle("ref" if os.path.exists(os.path.join(os.environ["DA_ROOT"], "oracle", "_ref", "libref.so")) else "port")  # the reference's own sources, live, where the build travelled
+same, chains = {}, {}
+for name in ("dup_cols", "neg_cols", "ones_wide", "ternary_sparse"):
+    k = structured_matrix(name)
+    for oname, kw in (("single", SINGLE_CHAIN), ("default", {})):
+        p, st = hip.solve_sharded(k, rank=0, world=1, **kw)
+        same[name + "/" + oname] = bool(p == O.solve(k, **kw))
+        chains[name + "/" + oname] = st["sharded_chains"]
+print(json.dumps({"same": same, "chains": chains}), flush=True)
+'''
+
 TWO = r'''
 import os, sys, json
 sys.path.insert(0, os.environ["DA_ROOT"]); sys.path.insert(0, os.path.join(os.environ["DA_ROOT"], "tests"))
@@ -42,12 +60,13 @@ os.environ["LOCAL_RANK"] = "0"   # both ranks on GPU 0
 from da4ml_amd import multi_gpu as mg
 from da4ml_amd import _binary as hip
 from oracle.oracle import Oracle
-from cases import int_matrix
+from cases import SINGLE_CHAIN, int_matrix, structured_matrix
 rank, world, local, device = mg.init("gloo")
 O = Oracle("ref" if os.path.exists(os.path.join(os.environ["DA_ROOT"], "oracle", "_ref", "libref.so")) else "port")  # the reference's own sources, live, where the build travelled
 same, steps = [], 0
 for k, kw in [(int_matrix(0, 16, 16, -128, 128), {}), (int_matrix(5, 64, 64, -128, 128), dict(method0="wmc", method1="wmc", decompose_dc=-1, search_all_decompose_dc=False)),
-              (int_matrix(2, 9, 21, -8, 8), dict(adder_size=1, carry_size=-1))]:
+              (int_matrix(2, 9, 21, -8, 8), dict(adder_size=1, carry_size=-1)),
+              (structured_matrix("dup_cols"), SINGLE_CHAIN)]:  # 4 columns tiled 16 times: equal columns on both sides of the split
     p, st = mg.solve_column_sharded(k, return_stats=True, **kw)
     same.append(bool(p == O.solve(k, **kw)))
     steps += st["greedy_steps"]
@@ -65,6 +84,17 @@ def test_sharded_phases_single_process():
     assert out['chains'] >= 10
 
 
+def test_sharded_phases_on_structured_matrices():
+    """the sharded kernels on equal, negated and doubled columns, on 300 all-ones columns (every column substituted in every step) and
+    on a 90 % sparse ternary matrix, as single chains and under the default search: each result equals the oracle's"""
+    env = dict(os.environ, DA_ROOT=str(ROOT))
+    r = subprocess.run([sys.executable, '-c', STRUCTURED_SINGLE], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert len(out['same']) == 8 and all(out['same'].values()), out
+    assert all(n >= 1 for n in out['chains'].values()), out
+
+
 def test_two_ranks_share_the_gpu_over_gloo():
     with socket.socket() as sock:
         sock.bind(('127.0.0.1', 0))
@@ -78,7 +108,7 @@ def test_two_ranks_share_the_gpu_over_gloo():
         assert p.returncode == 0, e[-3000:]
     res = [json.loads(o.strip().splitlines()[-1]) for o, _ in outs]
     for r in res:
-        assert all(r['same']) and len(r['same']) == 3, r
+        assert all(r['same']) and len(r['same']) == 4, r
     assert res[0]['steps'] == res[1]['steps'] > 500
 
 

@@ -37,6 +37,10 @@ def test_device_executor_on_a_solver_result():
     _in_child('body_solver_result')
 
 
+def test_device_executor_on_structured_solutions_in_several_tiles():
+    _in_child('body_structured_solutions')
+
+
 def body_golden_vectors():
     from da4ml_amd._binary import dais_interp_run
 
@@ -68,3 +72,28 @@ def body_solver_result():
     y = stage.predict(x, executor='device')
     assert np.array_equal(y[:2000], stage.predict(x[:2000]))
     assert np.array_equal(y, x @ stage.kernel.astype(np.float64))
+
+
+def body_structured_solutions():
+    """solutions of structured matrices (equal, negated and doubled columns; +-1 weights), 70 000 samples in tiles of 16 384 samples: four
+    whole tiles and a partial fifth whose last block is partial too, where every other device test fits one tile.  Both stages, each
+    on samples from all of its declared input range (the executors wrap every value into the format of its op's interval; stage 1
+    declares the intervals of stage 0's result ops before their output shifts): device == host executor == the matrix product"""
+    import os
+
+    os.environ['DA4ML_DAIS_TILE'] = '16384'  # read by the library at every call
+    from cases import SINGLE_CHAIN, samples_inside, structured_matrix
+
+    from da4ml_amd.cmvm import solve
+
+    rng = np.random.default_rng(2)
+    for name in ('neg_cols', 'ternary_dense'):
+        k = structured_matrix(name)
+        stage0, stage1 = solve(k, **SINGLE_CHAIN).solutions
+        for stage in (stage0, stage1):
+            x = samples_inside(stage, rng, 70_000)
+            y = stage.predict(x, executor='device')
+            assert np.array_equal(y, stage.predict(x)), name
+            assert np.array_equal(y, x @ stage.kernel.astype(np.float64)), name
+            if stage is stage0:
+                assert np.array_equal(y @ stage1.kernel.astype(np.float64), x @ k.astype(np.float64)), name
