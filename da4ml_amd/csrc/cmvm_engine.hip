@@ -59,6 +59,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "cmvm_core.h"
@@ -1336,8 +1337,13 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
 // k_iter_update), partner rows -- behind a pick that is either read from the descriptor (known one step ahead) or found by the block itself
 // (table_argmax_block).  SHARDED (cmvm_shard.h): the chain holds a slice of the columns and a replica of the pair table -- the six count vectors are
 // PARTIAL and go to the head of the exchange slab, and the block leaves one flag per row that shares a substituted column instead of a partner list.
+// MANYCOL: the carve for chains of up to 4095 columns, chosen by the host when the regular one does not fit beside the kernel's static arrays
+// (sel2_manycol, hip_chain_setup.h): 10 bytes per column instead of 36 in the wide layout.  B's list is not copied to LDS -- pass 1 reads and rewrites
+// the entry of a column where it lies in memory (every column is in A's list at most once, so no two threads touch the same entry; the barriers
+// that end the chunks of pass 1 order it before pass 2, which reads the entries back) --, the per-column arrays that hold values of at most n_out
+// are 16-bit, and the list length of a matched column is read from `collen` at the hit (it grows only after pass 1).
 // Returns 1 when the chain is (or just became) finished.
-template <class Cell, bool SHARDED = false> __device__ __forceinline__ int pick_body(ChainDev *g, unsigned int *n_done, int step) {
+template <class Cell, bool SHARDED = false, bool MANYCOL = false> __device__ __forceinline__ int pick_body(ChainDev *g, unsigned int *n_done, int step) {
     using O = CellOps<Cell>;
     using F = RowFmt<Cell>;
     using Entry = typename F::Entry;
@@ -1396,14 +1402,25 @@ template <class Cell, bool SHARDED = false> __device__ __forceinline__ int pick_
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // dynamic LDS carve: B's list | special-pair counters | per-matched-column scratch | column -> position in B
+    using Idx = std::conditional_t<MANYCOL, uint16_t, int>;                          // a column, or 1 + a position among at most n_out (< 4096)
     Entry *s_bent = reinterpret_cast<Entry *>(smem);                                  // [n_out] entries of row B (updated in place)
     uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_bent + n_out);                  // [6][Kpad]
     int *s_len = reinterpret_cast<int *>(s_cnt + 6 * Kpad);                           // [n_out + 1] list lengths of the matched columns
-    int *s_col = s_len + n_out + 1;                                                   // [n_out] matched columns
-    int *s_bpos = s_col + n_out;                                                      // [n_out] 1 + position of a column in B's list, 0 = absent
-    int *s_clen = s_bpos + n_out;                                                     // [n_out] list length of every column
-    int *s_cm = s_clen + n_out;                                                       // [n_out] 1 + index among the matched columns, 0 = not matched
+    Idx *s_col = reinterpret_cast<Idx *>(s_len + n_out + 1);                          // [n_out] matched columns
+    Idx *s_bpos = s_col + n_out;                                                      // [n_out] 1 + position of a column in B's list, 0 = absent
+    int *s_clen = reinterpret_cast<int *>(s_bpos + n_out);                            // [n_out] list length of every column
+    Idx *s_cm = reinterpret_cast<Idx *>(s_clen + n_out);                              // [n_out] 1 + index among the matched columns, 0 = not matched
     uint32_t *s_or = reinterpret_cast<uint32_t *>(s_cm + n_out);                      // [claim_words] OR of the substituted columns' row bitmaps (if it fits)
+    if constexpr (MANYCOL) {  // special-pair counters | matched lengths | claim area | three 16-bit per-column arrays; no copy of B's list, no lengths of all columns
+        s_bent = nullptr;
+        s_clen = nullptr;
+        s_cnt = reinterpret_cast<uint32_t *>(smem);
+        s_len = reinterpret_cast<int *>(s_cnt + 6 * Kpad);
+        s_or = reinterpret_cast<uint32_t *>(s_len + n_out + 1);
+        s_col = reinterpret_cast<Idx *>(s_or + claim_words);
+        s_bpos = s_col + n_out;
+        s_cm = s_bpos + n_out;
+    }
     constexpr int NW = SEL2_THREADS / WAVE;
     __shared__ int s_np, s_part[NW];
     __shared__ unsigned int s_matches;
@@ -1443,7 +1460,8 @@ template <class Cell, bool SHARDED = false> __device__ __forceinline__ int pick_
     }
     {
         // the list lengths of all columns (needed for the matched columns only, after the substitution) and the latency model's table
-        const int clen0 = collen[tid < n_out ? tid : 0];
+        int clen0 = 0;
+        if constexpr (!MANYCOL) clen0 = collen[tid < n_out ? tid : 0];
         const bool want_log2 = (adder_size >= 0 || carry_size >= 0) && tid < (int)(sizeof(Log2Table) / 4);
         const uint32_t l2w = want_log2 ? reinterpret_cast<const uint32_t *>(&c_log2)[tid] : 0u;
         if (tid == 0) {
@@ -1452,14 +1470,14 @@ template <class Cell, bool SHARDED = false> __device__ __forceinline__ int pick_
             g->c_n[par] = 0;  // this step's update appends to c_list[par] (last read by the selection of step - 1)
         }
         if (tid < n_out) {
-            s_clen[tid] = clen0;
+            if constexpr (!MANYCOL) s_clen[tid] = clen0;
             s_cm[tid] = 0;
             s_bpos[tid] = 0;
         }
         if (want_log2) reinterpret_cast<uint32_t *>(&s_log2)[tid] = l2w;
         for (int w = tid; w < claim_words; w += SEL2_THREADS) s_or[w] = 0;
         for (int j = tid + SEL2_THREADS; j < n_out; j += SEL2_THREADS) {
-            s_clen[j] = collen[j];
+            if constexpr (!MANYCOL) s_clen[j] = collen[j];
             s_cm[j] = 0;
             s_bpos[j] = 0;
         }
@@ -1529,13 +1547,13 @@ template <class Cell, bool SHARDED = false> __device__ __forceinline__ int pick_
     pin_vgpr(eA0, eB0);  // both consumed (waited for) here, in front of thread 0's stores below
     if (!same) {  // B's list into LDS, addressable by column (s_bpos was zeroed in the prologue, a barrier ago)
         if (tid < lenB) {
-            s_bent[tid] = eB0;
-            s_bpos[F::col(eB0)] = tid + 1;
+            if constexpr (!MANYCOL) s_bent[tid] = eB0;
+            s_bpos[F::col(eB0)] = (Idx)(tid + 1);
         }
         for (int t = tid + SEL2_THREADS; t < lenB; t += SEL2_THREADS) {
             const Entry e = rlB[t];
-            s_bent[t] = e;
-            s_bpos[F::col(e)] = t + 1;
+            if constexpr (!MANYCOL) s_bent[t] = e;
+            s_bpos[F::col(e)] = (Idx)(t + 1);
         }
     }
     if (tid == 0) {  // (a wait for a loaded value also waits for every store issued before it: these come after the last one)
@@ -1565,7 +1583,10 @@ template <class Cell, bool SHARDED = false> __device__ __forceinline__ int pick_
                 b = a;
             else {
                 pos = s_bpos[colA];
-                b = pos ? F::cell(s_bent[pos - 1]) : (Cell)0;
+                if constexpr (MANYCOL)
+                    b = pos ? F::cell(rlB[pos - 1]) : (Cell)0;
+                else
+                    b = pos ? F::cell(s_bent[pos - 1]) : (Cell)0;
             }
             if (a && b) substitute_column<Cell>(a, b, same, shift, sub, ma, mb);
             na = same ? (Cell)(a & ~ma & ~mb) : (Cell)(a & ~ma);
@@ -1585,20 +1606,27 @@ template <class Cell, bool SHARDED = false> __device__ __forceinline__ int pick_
         if (hit) {
             const int at = m + wbase + __popcll(bal & ((1ull << lane) - 1));
             rlA[t] = F::pack(colA, na);
-            if (!same) s_bent[pos - 1] = F::pack(colA, nbv);
+            if constexpr (MANYCOL) {
+                if (!same) rlB[pos - 1] = F::pack(colA, nbv);
+            } else {
+                if (!same) s_bent[pos - 1] = F::pack(colA, nbv);
+            }
             rlN[at] = F::pack(colA, ma);
             mcol[at] = (int)colA;
             mA[at] = ma;
             mB[at] = mb;
-            s_cm[colA] = at + 1;
+            s_cm[colA] = (Idx)(at + 1);
             {  // row bitmaps of this column: the new row enters, a row whose cell just lost its last digit leaves
                 DA_GLOBAL uint32_t *cb = colbits + (size_t)colA * cbw;
                 atomicOr(gen(&cb[Nw >> 5]), 1u << (Nw & 31));
                 if (na == 0) atomicAnd(gen(&cb[A >> 5]), ~(1u << (A & 31)));
                 if (!same && nbv == 0) atomicAnd(gen(&cb[B >> 5]), ~(1u << (B & 31)));
             }
-            s_len[at] = s_clen[colA];  // the pre-append length: the new row itself is not a partner
-            s_col[at] = (int)colA;
+            if constexpr (MANYCOL)
+                s_len[at] = collen[colA];
+            else
+                s_len[at] = s_clen[colA];  // the pre-append length: the new row itself is not a partner
+            s_col[at] = (Idx)colA;
             my_matches += popc32(O::plus(ma) | O::minus(ma));
         }
         // ---------------- (3) exact recount of the pairs among {A, B, new} (their old blocks are replaced); the
@@ -1617,8 +1645,13 @@ template <class Cell, bool SHARDED = false> __device__ __forceinline__ int pick_
     // pass 2: B's list back to memory, self pairs of what is left of B
     if (!same)
         for (int t = tid; t < lenB; t += SEL2_THREADS) {
-            const Entry e = s_bent[t];
-            rlB[t] = e;
+            Entry e;
+            if constexpr (MANYCOL)
+                e = rlB[t];  // (rewritten where it lies by pass 1)
+            else {
+                e = s_bent[t];
+                rlB[t] = e;
+            }
             const Cell nbv = F::cell(e);
             if (nbv) for_pairs_self<Cell>(nbv, nb, [&](int k) { atomicAdd(&cBB[k], 1u); });
         }
@@ -1767,7 +1800,7 @@ template <class Cell, bool SHARDED = false> __device__ __forceinline__ int pick_
 #ifndef DA_SEL2_WAVES
 #define DA_SEL2_WAVES 4  // wavefronts per SIMD the register budget of k_iter_select2 is capped for (measured 4 .. 8: the spills of 5 and more cost more than the smaller footprint gains)
 #endif
-template <class Cell, bool SHARDED = false> __global__ void __launch_bounds__(SEL2_THREADS) __attribute__((amdgpu_waves_per_eu(DA_SEL2_WAVES, DA_SEL2_WAVES))) k_iter_select2(ChainDev *chains, int n_chains, unsigned int *n_done, int step) {
+template <class Cell, bool SHARDED = false, bool MANYCOL = false> __global__ void __launch_bounds__(SEL2_THREADS) __attribute__((amdgpu_waves_per_eu(DA_SEL2_WAVES, DA_SEL2_WAVES))) k_iter_select2(ChainDev *chains, int n_chains, unsigned int *n_done, int step) {
     if ((int)blockIdx.x >= n_chains) return;
 #ifdef DA_STEP_CLOCKS
     {
@@ -1791,7 +1824,7 @@ template <class Cell, bool SHARDED = false> __global__ void __launch_bounds__(SE
     if (blockIdx.y == 0)
         search_body<Cell>(&chains[blockIdx.x], step);
     else
-        (void)pick_body<Cell, SHARDED>(&chains[blockIdx.x], n_done, step);
+        (void)pick_body<Cell, SHARDED, MANYCOL>(&chains[blockIdx.x], n_done, step);
 #ifdef DA_STEP_CLOCKS
     __syncthreads();
     if (threadIdx.x == 0) CLK_MARK(&chains[blockIdx.x], step & 1, 1, false);

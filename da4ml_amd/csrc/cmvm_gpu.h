@@ -23,6 +23,7 @@ struct GpuTimings {  // accumulated since the last reset; read by the benchmark 
     // sampled per-kernel durations (HIP events around the first group's kernels in the first lockstep iteration of every window)
     double select_ms_sampled = 0, update_ms_sampled = 0;
     long long samples = 0;
+    long long manycol_chains = 0;  // chains that ran the many-column instantiation of k_iter_select2 (sel2_manycol)
     double sampled_chain_launches = 0;  // sum over sampled launches of the number of chains in that launch
     // algorithmic-traffic counters of k_iter_update, summed over chains
     long long found = 0, inserts = 0, cell_reads = 0;

@@ -152,7 +152,11 @@ void stage1_distances(Backend &be, Stage1 &s) {
     s.have_dist = true;
 }
 
-// Prim's tree from vertex 0 with the reference's scan order and optional depth cap (mat_decompose.cc:6-60)
+// Prim's tree from vertex 0 with the reference's scan order and optional depth cap (mat_decompose.cc:6-60).  The reference scans all
+// (i outside, j inside) pairs in every step and keeps the first strict minimum: V^3 / 6 edge costs, a minute for the 4096 vertices of a
+// 4095-column kernel.  The cost of an edge (i, j) is fixed once j is in the tree (its depth is), so every outside vertex keeps its
+// cheapest edge into the tree, the one to the smallest j among equals, and a step takes the smallest i among the cheapest: the same pair
+// the scan finds, in V^2 edge costs.
 std::vector<std::pair<int, int>> spanning_tree(const std::vector<int64_t> &cost, int V, int dc) {
     auto edge_lat = [&](int i, int j) { return std::ceil(std::log2((float)std::max<int64_t>(cost[(size_t)i * V + j], 1))); };
     std::vector<char> in_tree(V, 0);
@@ -164,27 +168,38 @@ std::vector<std::pair<int, int>> spanning_tree(const std::vector<int64_t> &cost,
         cap = (float)((std::pow(2.0, dc) - 1) + std::ceil(std::log2(top + 1e-32)));
     }
     const int64_t blocked = std::numeric_limits<int64_t>::max() / 2;
+    auto edge_cost = [&](int i, int j) {  // of i outside to j inside
+        if (dc >= 0 && std::max(edge_lat(i, j), (float)depth[j]) + 1 > cap) return blocked;
+        return cost[(size_t)i * V + j];
+    };
+    std::vector<int64_t> key(V, std::numeric_limits<int64_t>::max());  // cheapest edge of an outside vertex into the tree
+    std::vector<int> to(V, -1);                                        // its inside end: the smallest j of that cost
+    auto joined = [&](int j) {
+        for (int i = 0; i < V; ++i) {
+            if (in_tree[i]) continue;
+            const int64_t c = edge_cost(i, j);
+            if (c < key[i] || (c == key[i] && j < to[i])) {
+                key[i] = c;
+                to[i] = j;
+            }
+        }
+    };
+    joined(0);
     std::vector<std::pair<int, int>> edges;
     edges.reserve(V > 0 ? V - 1 : 0);
     for (int step = 1; step < V; ++step) {
         int64_t best = std::numeric_limits<int64_t>::max();
-        int bi = -1, bj = -1;
-        for (int i = 0; i < V; ++i) {
-            if (in_tree[i]) continue;
-            for (int j = 0; j < V; ++j) {
-                if (!in_tree[j]) continue;
-                int64_t c = cost[(size_t)i * V + j];
-                if (dc >= 0 && std::max(edge_lat(i, j), (float)depth[j]) + 1 > cap) c = blocked;
-                if (c < best) {
-                    best = c;
-                    bi = i;
-                    bj = j;
-                }
+        int bi = -1;
+        for (int i = 0; i < V; ++i)
+            if (!in_tree[i] && key[i] < best) {
+                best = key[i];
+                bi = i;
             }
-        }
+        const int bj = to[bi];
         in_tree[bi] = 1;
         depth[bi] = (int32_t)(std::max(edge_lat(bi, bj), (float)depth[bj]) + 1);
         edges.emplace_back(bj, bi);
+        joined(bi);
     }
     return edges;
 }

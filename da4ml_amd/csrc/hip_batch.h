@@ -28,13 +28,16 @@ struct HipBackend::Impl::Batch {
     std::vector<Geometry> geo;
     std::vector<size_t> a_off;  // of every chain in the arena
     size_t arena_bytes = 0, budget = 0, free_b = 0;
-    std::vector<int> order;  // descriptor s of the device is chain order[s] of the call: narrow chains first
+    std::vector<int> order;  // descriptor s of the device is chain order[s] of the call: narrow chains first, and of a width those of the regular selection carve first
+    std::vector<char> manycol;  // per chain: it runs the many-column instantiation of k_iter_select2 (sel2_manycol)
+    static constexpr int N_VAR = 4;  // kernel variants of a batch: 2 * wide + manycol
+    int variant(int i) const { return 2 * (int)geo[i].wide + (int)manycol[i]; }
     struct Range {
         int first, count;
-        bool wide;
-    } ranges[2];
-    size_t sel_lds[2] = {0, 0}, upd_lds[2] = {0, 0};  // per width: dynamic LDS of the loop's kernels, k_iter_update blocks per chain
-    int upd_blocks[2] = {1, 1};
+        bool wide, manycol;
+    } ranges[N_VAR];
+    size_t sel_lds[N_VAR] = {0, 0, 0, 0}, upd_lds[N_VAR] = {0, 0, 0, 0};  // per variant: dynamic LDS of the loop's kernels, k_iter_update blocks per chain
+    int upd_blocks[N_VAR] = {1, 1, 1, 1};
     EventGuard events;  // declared before anything greedy_loop declares: destroyed after its streams have been drained, and after extract has read the clocks
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> sample_ev;  // three per sampled iteration
@@ -97,9 +100,11 @@ struct HipBackend::Impl::Batch {
     // ---- 3. arena, descriptors, initial state; launch sizes per cell width (descriptors are grouped so that one launch covers a contiguous range)
     void init_chains() {
         unsigned char *arena = static_cast<unsigned char *>(im.arena.get(arena_bytes));
+        manycol.resize(n);
         for (int i = 0; i < n; ++i) {
             carve_chain(arena + a_off[i], jobs[i].n_out, geo[i], desc[i]);
-            apply_geometry(desc[i], geo[i], sel2_lds_budget(im.device, geo[i].wide));
+            manycol[i] = sel2_manycol(im.device, jobs[i].n_out, geo[i], im.manycol_from);
+            apply_geometry(desc[i], geo[i], sel2_lds_budget(im.device, geo[i].wide, manycol[i]), manycol[i]);
             desc[i].done = (jobs[i].method == M_DUMMY || jobs[i].method < 0) ? 1 : 0;
         }
         for (int i = 0; i < n; ++i) upload_step_table(desc[i], step_tabs[i], st);
@@ -111,7 +116,7 @@ struct HipBackend::Impl::Batch {
 
         order.resize(n);
         std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return geo[a].wide < geo[b].wide; });
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return variant(a) < variant(b); });
         bool permuted = false;
         for (int i = 0; i < n; ++i) permuted |= order[i] != i;
         if (permuted) {
@@ -120,26 +125,25 @@ struct HipBackend::Impl::Batch {
             HIP_CHECK(hipMemcpyAsync(d_desc, sorted.data(), sizeof(ChainDev) * (size_t)n, hipMemcpyHostToDevice, st));
             HIP_CHECK(hipStreamSynchronize(st));
         }
-        int n_narrow = 0;
-        for (int i = 0; i < n; ++i) n_narrow += !geo[i].wide;
-        ranges[0] = Range{0, n_narrow, false};
-        ranges[1] = Range{n_narrow, n - n_narrow, true};
+        int n_of[N_VAR] = {0, 0, 0, 0};
+        for (int i = 0; i < n; ++i) ++n_of[variant(i)];
+        for (int v = 0, first = 0; v < N_VAR; first += n_of[v], ++v) ranges[v] = Range{first, n_of[v], v >= 2, (v & 1) != 0};
 
-        size_t pair_lds[2] = {0, 0};
-        long long max_pairs[2] = {0, 0};
+        size_t pair_lds[N_VAR] = {0, 0, 0, 0};
+        long long max_pairs[N_VAR] = {0, 0, 0, 0};
         for (int i = 0; i < n; ++i) {
-            int w = geo[i].wide;
+            const int w = variant(i);
             const size_t no = (size_t)jobs[i].n_out, cellb = geo[i].wide ? 8 : 4;
-            const size_t s = align_up(sel2_fixed_lds(jobs[i].n_out, geo[i]) + (size_t)desc[i].claim_words * 4, 16);
-            if (s > sel2_lds_budget(im.device, geo[i].wide))
-                throw std::runtime_error("selection kernel needs " + std::to_string(s) + " bytes of dynamic LDS, the device leaves it " + std::to_string(sel2_lds_budget(im.device, geo[i].wide)) +
-                                         " beside the kernel's static arrays (n_out too large)");
+            const size_t s = align_up(sel2_fixed_lds(jobs[i].n_out, geo[i], manycol[i]) + (size_t)desc[i].claim_words * 4, 16);
+            if (s > sel2_lds_budget(im.device, geo[i].wide, manycol[i]))
+                throw std::runtime_error("selection kernel needs " + std::to_string(s) + " bytes of dynamic LDS, the device leaves it " +
+                                         std::to_string(sel2_lds_budget(im.device, geo[i].wide, manycol[i])) + " beside the kernel's static arrays (n_out too large)");
             sel_lds[w] = std::max(sel_lds[w], s);
             upd_lds[w] = std::max(upd_lds[w], align_up(2 * no * cellb + no * 6, 16) + align_up((size_t)UPD_WAVES * (QN * 3 + 1) * (size_t)geo[i].Kpad * 4, 16));  // UpdLds: hand-off tables | counters
             pair_lds[w] = std::max(pair_lds[w], (size_t)4 * geo[i].Kpad * 4);
             max_pairs[w] = std::max(max_pairs[w], (long long)jobs[i].n_in * (jobs[i].n_in + 1) / 2);
         }
-        for (int w = 0; w < 2; ++w) {
+        for (int w = 0; w < N_VAR; ++w) {
             const Range &r = ranges[w];
             if (r.count == 0) continue;
             upd_blocks[w] = std::max(2, std::min(64, (im.upd_total_blocks + r.count - 1) / r.count));  // at least 2 and at most 64 blocks per chain
@@ -151,8 +155,9 @@ struct HipBackend::Impl::Batch {
             });
             HIP_CHECK(hipGetLastError());
         }
-        for (int w = 0; w < 2; ++w)
-            if (ranges[w].count) sel2_allow_lds<false>(ranges[w].wide, sel_lds[w]);
+        for (int w = 0; w < N_VAR; ++w)
+            if (ranges[w].count) sel2_allow_lds<false>(ranges[w].wide, sel_lds[w], ranges[w].manycol);
+        for (int wide = 0; wide < 2; ++wide) upd_allow_lds(im.device, wide != 0, std::max(upd_lds[2 * wide], upd_lds[2 * wide + 1]));  // (one kernel for both carves of a width)
         HIP_CHECK(hipStreamSynchronize(st));
     }
 
@@ -166,15 +171,17 @@ struct HipBackend::Impl::Batch {
         HIP_CHECK(hipEventRecord(ev0, st));
         HIP_CHECK(hipStreamSynchronize(st));  // set-up done before the group streams start
         struct Group {
-            int first, count, w;  // descriptor range, cell width index
+            int first, count, w;  // descriptor range, kernel variant (index of its range)
             hipStream_t stream;
         };
         std::vector<Group> groups;
-        for (int w = 0; w < 2; ++w) {
+        int n_ranges = 0;
+        for (int w = 0; w < N_VAR; ++w) n_ranges += ranges[w].count != 0;
+        for (int w = 0; w < N_VAR; ++w) {
             const Range &r = ranges[w];
             if (r.count == 0) continue;
             int parts = std::max(1, std::min(im.n_lanes, r.count / 8));
-            if (ranges[0].count && ranges[1].count) parts = std::max(1, parts / 2);
+            if (n_ranges > 1) parts = std::max(1, parts / n_ranges);  // (at most MAX_LANES groups in all)
             for (int p = 0; p < parts; ++p) {
                 int lo = r.first + (int)((long long)r.count * p / parts), hi = r.first + (int)((long long)r.count * (p + 1) / parts);
                 groups.push_back(Group{lo, hi - lo, w, im.lanes[groups.size() % Impl::MAX_LANES]});
@@ -193,10 +200,10 @@ struct HipBackend::Impl::Batch {
             const dim3 sel_grid((gr.count + 7) & ~7, 2);  // y = 0 search block, y = 1 substitution block
             // (+ 2: the last two blocks of a chain write the six blocks of the pairs among the modified rows)
             const dim3 upd_grid((gr.count + 7) & ~7, upd_blocks[gr.w] + 2);
-            with_cell(gr.w != 0, [&](auto c) {
+            with_sel2(ranges[gr.w].wide, ranges[gr.w].manycol, [&](auto c, auto mc) {
                 using Cell = decltype(c);
                 if (se) HIP_CHECK(hipEventRecord(se[0], gr.stream));
-                hipLaunchKernelGGL(k_iter_select2<Cell>, sel_grid, dim3(SEL2_THREADS), sel_lds[gr.w], gr.stream, base, gr.count, im.d_done, step);
+                hipLaunchKernelGGL((k_iter_select2<Cell, false, decltype(mc)::value>), sel_grid, dim3(SEL2_THREADS), sel_lds[gr.w], gr.stream, base, gr.count, im.d_done, step);
                 if (se) HIP_CHECK(hipEventRecord(se[1], gr.stream));
                 with_flag(with_stats, [&](auto s) {
                     hipLaunchKernelGGL((k_iter_update<Cell, decltype(s)::value>), upd_grid, dim3(UPD_THREADS), upd_lds[gr.w], gr.stream, base, gr.count);
@@ -330,7 +337,7 @@ struct HipBackend::Impl::Batch {
 
     // ---- 5. extraction, the final descriptors and the loop's clocks; every outs[] reset to what its chain reports.  True: some chain outgrew its arena
     bool extract() {
-        for (int w = 0; w < 2; ++w) {
+        for (int w = 0; w < N_VAR; ++w) {
             const Range &r = ranges[w];
             if (r.count == 0) continue;
             const dim3 colgrid((max_n_out + 3) / 4, r.count);
@@ -448,6 +455,7 @@ struct HipBackend::Impl::Batch {
         tm.host_launch_ms += host_launch_ms;
         tm.lockstep_iters += launched_iters;
         tm.chains += n;
+        for (int i = 0; i < n; ++i) tm.manycol_chains += manycol[i] ? 1 : 0;
         tm.arena_bytes = std::max(tm.arena_bytes, (double)arena_bytes);
     }
 };

@@ -22,6 +22,7 @@ struct HipBackend::Impl {
     hipStream_t poll_stream = nullptr;
     GpuTimings timings;
     double table_scale = 1.0;  // grows on E_TABLE_CAPACITY retries
+    int manycol_from = 0;  // chains of at least so many columns run the many-column selection kernel whatever fits (0: only those whose regular carve does not fit); DA4ML_HIP_MANYCOL_FROM
     struct Batch;  // the state of one run_chains call
 };
 
@@ -32,6 +33,7 @@ HipBackend::HipBackend(int device) : impl_(new Impl) {
     impl_->lanes[0] = impl_->stream;  // the first group runs on the main stream (hardware queues are a scarce resource)
     for (int l = 1; l < Impl::MAX_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&impl_->lanes[l], hipStreamNonBlocking));
     if (const char *e = std::getenv("DA4ML_HIP_TABLE_SCALE")) impl_->table_scale = std::max(1e-4, std::atof(e));
+    if (const char *e = std::getenv("DA4ML_HIP_MANYCOL_FROM")) impl_->manycol_from = std::max(0, std::atoi(e));
     if (const char *e = std::getenv("DA4ML_HIP_ROW_SCALE")) row_scale_ = std::max(1e-4, std::atof(e));
     if (const char *e = std::getenv("DA4ML_HIP_UPD_BLOCKS")) impl_->upd_total_blocks = std::max(2, std::atoi(e));
     if (const char *e = std::getenv("DA4ML_HIP_LAUNCH_THREADS")) impl_->launch_threads = std::max(1, std::atoi(e));
@@ -64,11 +66,21 @@ struct Geometry {
     uint32_t C, rl_cap;
 };
 
-// raises the dynamic-LDS limit of the selection kernel the chains of that width are about to be launched with
-template <bool SHARDED> void sel2_allow_lds(bool wide, size_t bytes) {
-    with_cell(wide, [&](auto c) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_select2<decltype(c), SHARDED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    });
+// The unsharded instantiation of k_iter_select2 for a cell width and a carve of the substitution block: f(Cell{}, std::bool_constant<MANYCOL>{})
+template <class F> void with_sel2(bool wide, bool manycol, F &&f) {
+    with_cell(wide, [&](auto c) { with_flag(manycol, [&](auto mc) { f(c, mc); }); });
+}
+// raises the dynamic-LDS limit of the selection kernel the chains of that width and carve are about to be launched with (column-sharded
+// chains have the regular carve only)
+template <bool SHARDED> void sel2_allow_lds(bool wide, size_t bytes, bool manycol = false) {
+    if constexpr (SHARDED)
+        with_cell(wide, [&](auto c) {
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_select2<decltype(c), true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        });
+    else
+        with_sel2(wide, manycol, [&](auto c, auto mc) {
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_select2<decltype(c), false, decltype(mc)::value>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        });
 }
 
 // Byte offsets of a chain's inputs in an io buffer: kernel | qints | lats | xint (the centred matrix, written by k_prepare) | shift0 | shift1, each
@@ -106,34 +118,59 @@ void fill_job(ChainDev &d, const ChainJob &j, int n_loc, int col0, unsigned char
     d.shift1 = reinterpret_cast<int8_t *>(io + L.shift1);
 }
 
-// Dynamic LDS of a k_iter_select2 block WITHOUT the optional claim area (pick_body's carve): B's list, six count vectors, five per-column arrays
-size_t sel2_fixed_lds(int n_out, const Geometry &g) {
+// Dynamic LDS of a k_iter_select2 block WITHOUT the optional claim area (pick_body's carve).  Regular: B's list, six count vectors, five per-column
+// arrays.  Many-column: six count vectors, the matched columns' list lengths, three 16-bit per-column arrays (B's list stays in memory)
+size_t sel2_fixed_lds(int n_out, const Geometry &g, bool manycol = false) {
     const size_t no = (size_t)n_out, entb = g.wide ? 16 : 4;
+    if (manycol) return 6 * (size_t)g.Kpad * 4 + (no + 1) * 4 + 3 * no * 2;
     return no * entb + 6 * (size_t)g.Kpad * 4 + (5 * no + 1) * 4;
 }
 // What the device leaves for it: the per-workgroup LDS limit less the kernel's STATIC __shared__ arrays (the search block's bound / work lists,
-// the substitution block's partner ids: ~75 KB -- asked from the runtime, not assumed), less a small reserve.  Static + dynamic beyond the limit
+// the substitution block's partner ids: 42 768 bytes with 2048 group records -- asked from the runtime, not assumed), less a small reserve.  Static + dynamic beyond the limit
 // fails in hipFuncSetAttribute or at launch with a raw HIP error; the caller turns it into a clear message.
-size_t sel2_lds_budget(int device, bool wide) {
+size_t sel2_lds_budget(int device, bool wide, bool manycol = false) {
     static std::mutex mu;
-    static size_t cached[2] = {0, 0};
+    static size_t cached[2][2] = {{0, 0}, {0, 0}};
     std::lock_guard<std::mutex> lk(mu);
-    if (!cached[wide]) {
+    if (!cached[wide][manycol]) {
         hipFuncAttributes fa;
-        const void *fn = wide ? reinterpret_cast<const void *>(&k_iter_select2<uint64_t>) : reinterpret_cast<const void *>(&k_iter_select2<uint32_t>);
+        const void *fn = nullptr;
+        with_sel2(wide, manycol, [&](auto c, auto mc) { fn = reinterpret_cast<const void *>(&k_iter_select2<decltype(c), false, decltype(mc)::value>); });
         HIP_CHECK(hipFuncGetAttributes(&fa, fn));
         int limit = 0;
         HIP_CHECK(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
         if (limit < 64 * 1024) limit = 64 * 1024;
         const size_t used = fa.sharedSizeBytes + 256;
-        cached[wide] = (size_t)limit > used ? (size_t)limit - used : 1;
+        cached[wide][manycol] = (size_t)limit > used ? (size_t)limit - used : 1;
     }
-    return cached[wide];
+    return cached[wide][manycol];
+}
+// The carve a chain of a batch runs with: the regular one whenever its fixed part fits (then the chain runs exactly the kernel it always ran);
+// the many-column one beyond that, and from `manycol_from` columns on when that knob is set
+bool sel2_manycol(int device, int n_out, const Geometry &g, int manycol_from) {
+    return (manycol_from > 0 && n_out >= manycol_from) || align_up(sel2_fixed_lds(n_out, g), 16) > sel2_lds_budget(device, g.wide);
+}
+// k_iter_update's dynamic LDS (UpdLds: the hand-off tables, 22 bytes per column in the wide layout, and the waves' counters) passes the 64 KB a
+// kernel may ask for without further ado from about 2800 columns on: the limit of its instantiations of that width is raised then, after a check
+// against what the device has per workgroup.  Chains whose blocks ask for no more than 64 KB launch as they always did: nothing is queried or set.
+void upd_allow_lds(int device, bool wide, size_t bytes) {
+    if (bytes <= 64 * 1024) return;
+    hipFuncAttributes fa;
+    with_cell(wide, [&](auto c) { HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_iter_update<decltype(c), false>))); });
+    int limit = 0;
+    HIP_CHECK(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    if (fa.sharedSizeBytes + bytes > (size_t)limit)
+        throw std::runtime_error("update kernel needs " + std::to_string(bytes) + " bytes of dynamic LDS beside " + std::to_string(fa.sharedSizeBytes) +
+                                 " of static arrays, the device has " + std::to_string(limit) + " per workgroup (n_out too large)");
+    with_cell(wide, [&](auto c) {
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    });
 }
 // words of the optional LDS area in which the substitution block combines the row bitmaps of a young chain: dropped (0: every wave ORs its words
 // itself) when it does not fit beside the rest -- the kernel runs either way
-int claim_words_for(int n_out, const Geometry &g, size_t budget) {
-    const size_t words = ((size_t)g.rcap + 31) / 32, fixed = align_up(sel2_fixed_lds(n_out, g), 16);
+int claim_words_for(int n_out, const Geometry &g, size_t budget, bool manycol = false) {
+    const size_t words = ((size_t)g.rcap + 31) / 32, fixed = align_up(sel2_fixed_lds(n_out, g, manycol), 16);
     return words * 4 <= 64 * 1024 && fixed + words * 4 + 16 <= budget ? (int)words : 0;
 }
 
@@ -207,7 +244,7 @@ size_t carve_chain(unsigned char *base, int n_loc, const Geometry &g, ChainDev &
 }
 
 // The geometry into a descriptor whose job fields are set and whose arrays carve_chain has assigned: the chain before its first step
-void apply_geometry(ChainDev &d, const Geometry &g, size_t lds_budget) {
+void apply_geometry(ChainDev &d, const Geometry &g, size_t lds_budget, bool manycol = false) {
     d.n_bits = g.n_bits;
     d.K = g.K;
     d.Kpad = g.Kpad;
@@ -221,7 +258,7 @@ void apply_geometry(ChainDev &d, const Geometry &g, size_t lds_budget) {
     d.rl_cap = g.rl_cap;
     d.rl_used = (uint32_t)d.n_in * (uint32_t)d.n_out;
     d.n_rows = d.n_in;
-    d.claim_words = claim_words_for(d.n_out, g, lds_budget);
+    d.claim_words = claim_words_for(d.n_out, g, lds_budget, manycol);
     d.iter = 0;
     d.cb_words = (g.rcap + 31) / 32;
     d.n_step_mant = g.n_mant;

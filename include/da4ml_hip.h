@@ -15,8 +15,10 @@
  *
  * Size limits of a solve (DA_ERR_RUNTIME with a message beyond them): up to 2048 input rows are supported (pair tables of up to
  * 2^30 slots; a chain whose arena does not fit into the free device memory is refused with the MiB it needs and the MiB that are
- * free); n_out is limited to about 2300 by the selection kernel's LDS and to below 4096 by the row-reference format; a chain holds
- * fewer than 2^24 rows and 2^28 row-list entries; at most 30 CSD digits per entry.
+ * free); up to 4095 output columns are supported, the limit of the row-reference format (from about 3300 columns on a chain runs the
+ * many-column form of the selection kernel, which works on one of the two row lists in memory instead of LDS; DA4ML_HIP_MANYCOL_FROM=<n_out>
+ * forces that form from a width on); a column-sharded chain (da_solve_sharded) keeps the regular form and so about 3300 columns per rank; a
+ * chain holds fewer than 2^24 rows and 2^28 row-list entries; at most 30 CSD digits per entry.
  */
 #ifndef DA4ML_HIP_H
 #define DA4ML_HIP_H
@@ -166,7 +168,7 @@ int da_dais_run_on(const int32_t *program, int64_t n_words, const double *inputs
 int da_timings(double *t, int reset);  /* (blocks found / created are tallied only under DA4ML_HIP_STATS=1, see da_result_stats) */
 /* Further engine counters, same accumulation and reset as da_timings (call BEFORE a resetting da_timings); writes min(n, 16) values:
  * out[0] algorithmic bytes of k_iter_select (device-counted), out[1] host ms spent queueing greedy-loop
- * launches, out[2..15] reserved (0); returns the number written */
+ * launches, out[14] chains that ran the many-column form of the selection kernel, the others reserved; returns the number written */
 int da_engine_stats(double *out, int n);
 
 #ifdef __cplusplus
