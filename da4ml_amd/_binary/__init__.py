@@ -27,7 +27,7 @@ _i32p = np.ctypeslib.ndpointer(np.int32, flags='C_CONTIGUOUS')
 
 EXPORTS = (
     'da_last_error da_last_error_code da_version da_device_count da_set_device da_get_lsb_loc da_iceil_log2 da_cost_add da_int_arr_to_csd '
-    'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
+    'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_batch_seeded da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
     'da_result_stats da_free da_timings da_engine_stats da_dais_run da_dais_last_error da_dais_run_on'
 ).split()
 
@@ -85,6 +85,8 @@ def lib():
     L.da_solve.restype = C.c_void_p
     L.da_solve.argtypes = [_f32p, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.da_solve_batch.argtypes = [C.c_int, C.c_void_p, _i64p, _i64p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]  # fmt: skip
+    if hasattr(L, 'da_solve_batch_seeded'):  # (as da_shard_exchanged_elements below: libraries of earlier revisions lack it; asking one for seeds raises)
+        L.da_solve_batch_seeded.argtypes = L.da_solve_batch.argtypes[:-1] + [C.c_void_p, C.c_void_p]
     L.da_solve_sharded.restype = C.c_void_p
     L.da_solve_sharded.argtypes = [_f32p, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, _i64p]  # fmt: skip
@@ -327,15 +329,26 @@ def solve_many(
     carry_size: int = -1,
     search_all_decompose_dc: bool = True,
     _stats: bool = False,
+    seeds=None,
 ):
     """Solve independent matrices concurrently on the GPU (addition to the reference API; same options as ``solve``).
 
     ``qintervals`` / ``latencies`` are ``None`` or per-kernel lists (entries may be ``None``).
+
+    ``seeds``: ``None`` (every problem gets the reference's result) or one unsigned 64-bit tie seed per kernel
+    (``da_solve_batch_seeded``, include/da4ml_hip.h): a problem with a seed other than 0 settles equally scored pairs of its greedy
+    chains by the order that seed gives instead of the reference's -- a random restart of the search; the same seed gives the same
+    result in every batch.  ``da4ml_amd.cmvm.solve_restarts`` is the user-facing entry.
     """
     ks = [_kernel(k) for k in kernels]
     n = len(ks)
     if n == 0:
         return []
+    seed_arr = None
+    if seeds is not None:
+        if len(seeds) != n:
+            raise ValueError('seeds must hold one entry per kernel')
+        seed_arr = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds], np.uint64)
     n_in = np.array([k.shape[0] for k in ks], np.int64)
     n_out = np.array([k.shape[1] for k in ks], np.int64)
     kptr = (C.c_void_p * n)(*[k.ctypes.data for k in ks])
@@ -349,8 +362,14 @@ def solve_many(
             ls.append(None if l is None else l.ctypes.data)
         qptr, lptr = (C.c_void_p * n)(*qs), (C.c_void_p * n)(*ls)
     res = (C.c_void_p * n)()
-    rc = lib().da_solve_batch(n, kptr, n_in, n_out, method0.encode(), method1.encode(), int(hard_dc), int(decompose_dc), qptr, lptr,
-                              int(adder_size), int(carry_size), int(bool(search_all_decompose_dc)), res)  # fmt: skip
+    if seed_arr is None:
+        rc = lib().da_solve_batch(n, kptr, n_in, n_out, method0.encode(), method1.encode(), int(hard_dc), int(decompose_dc), qptr, lptr,
+                                  int(adder_size), int(carry_size), int(bool(search_all_decompose_dc)), res)  # fmt: skip
+    else:
+        if not hasattr(lib(), 'da_solve_batch_seeded'):
+            raise RuntimeError(f'{_LIB_PATH} has no da_solve_batch_seeded: tie seeds need the library of this revision')
+        rc = lib().da_solve_batch_seeded(n, kptr, n_in, n_out, method0.encode(), method1.encode(), int(hard_dc), int(decompose_dc), qptr, lptr,
+                                         int(adder_size), int(carry_size), int(bool(search_all_decompose_dc)), seed_arr.ctypes.data, res)  # fmt: skip
     if rc != 0:
         _raise(rc)
     return [_collect(res[i], _stats) for i in range(n)]

@@ -175,10 +175,10 @@ int da_kernel_decompose(const float *kernel, int64_t n_in, int64_t n_out, int dc
     }
 }
 
-int da_solve_batch(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const char *method0,
-                   const char *method1, int hard_dc, int decompose_dc, const float *const *qintervals,
-                   const float *const *latencies, int adder_size, int carry_size, int search_all_decompose_dc,
-                   da_result **results) {
+int da_solve_batch_seeded(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const char *method0,
+                          const char *method1, int hard_dc, int decompose_dc, const float *const *qintervals,
+                          const float *const *latencies, int adder_size, int carry_size, int search_all_decompose_dc,
+                          const uint64_t *seeds, da_result **results) {
     std::lock_guard<LibraryMutex> lk(g_mutex);
     try {
         std::vector<da::Problem> probs((size_t)count);
@@ -201,6 +201,7 @@ int da_solve_batch(int count, const float *const *kernels, const int64_t *n_in, 
             p.opt.adder_size = adder_size;
             p.opt.carry_size = carry_size;
             p.opt.search_all = search_all_decompose_dc != 0;
+            p.opt.seed = seeds ? seeds[i] : 0;
         }
         std::vector<da::ChainStats> stats;
         const auto t0 = std::chrono::steady_clock::now();
@@ -212,6 +213,14 @@ int da_solve_batch(int count, const float *const *kernels, const int64_t *n_in, 
     } catch (const std::exception &e) {
         return fail(e);
     }
+}
+
+int da_solve_batch(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const char *method0,
+                   const char *method1, int hard_dc, int decompose_dc, const float *const *qintervals,
+                   const float *const *latencies, int adder_size, int carry_size, int search_all_decompose_dc,
+                   da_result **results) {
+    return da_solve_batch_seeded(count, kernels, n_in, n_out, method0, method1, hard_dc, decompose_dc, qintervals, latencies, adder_size, carry_size,
+                                 search_all_decompose_dc, nullptr, results);
 }
 
 da_result *da_solve(const float *kernel, int64_t n_in, int64_t n_out, const char *method0, const char *method1, int hard_dc,

@@ -296,6 +296,55 @@ DA_HD uint64_t tie_word(uint32_t id0, uint32_t id1, int idx) {
     return ((uint64_t)id1 << 31) | ((uint64_t)id0 << 7) | (uint64_t)idx;
 }
 
+// ------------------------------------------------------------------------------------ seeded tie order
+// A chain with a tie seed != 0 settles equal ranks by another strict total order: a random restart of the greedy search.  Only ties
+// move: ranks (scores) are what they were, so every such run is a greedy run of the reference's method.  The word keeps the shape
+// of the reference's -- 48 bits of the row pair above 7 bits of the key index, below 2^55 -- so that bound words (rank << 32 | tie
+// >> 23) order coarser than (rank, tie) as before:
+//   * high part: a keyed bijection of the 48 bits (id1 << 24 | id0), invertible steps only -- xor with the seed's low 48 bits,
+//     multiply by an odd constant mod 2^48, xor-shift by 24 (its own inverse on 48 bits), xor with the seed's high 48 bits.  The
+//     rows of an entry are read back from its word (tie_word_rows);
+//   * low part: idx ^ k7, k7 = the seed's top seven bits.  Inside a block (one row pair) the order of the keys is therefore the
+//     order of (idx ^ k7): the best entry of a block is the maximum of (rank << 8 | (idx ^ k7)), see tie_block_pos.
+// Injective in (id0, id1, idx) for ids < 2^24 and idx < 128.  tie_word_seeded wants seed != 0; the four-argument tie_word takes any.
+constexpr uint64_t TIE_PAIR_MASK = (1ull << 48) - 1;
+constexpr uint64_t TIE_MUL = 0x9E3779B97F4Bull;  // odd
+constexpr uint64_t tie_mul_inverse(uint64_t m) {  // Newton's iteration: correct bits double, from the three of m * m == 1 (mod 8)
+    uint64_t x = m;
+    for (int i = 0; i < 5; ++i) x *= 2 - m * x;
+    return x & TIE_PAIR_MASK;
+}
+constexpr uint64_t TIE_MUL_INV = tie_mul_inverse(TIE_MUL);
+static_assert(((TIE_MUL * TIE_MUL_INV) & TIE_PAIR_MASK) == 1, "inverse of the tie multiplier mod 2^48");
+DA_HD uint32_t tie_k7(uint64_t seed) { return (uint32_t)(seed >> 57); }
+// position of key `idx` in the within-block order of a seeded chain, and back (an involution); values stay below 128
+DA_HD uint32_t tie_block_pos(uint32_t idx, uint64_t seed) { return idx ^ tie_k7(seed); }
+DA_HD uint64_t tie_pair_mix(uint64_t pair, uint64_t seed) {  // the bijection of (id1 << 24 | id0)
+    uint64_t h = pair ^ (seed & TIE_PAIR_MASK);
+    h = (h * TIE_MUL) & TIE_PAIR_MASK;
+    h ^= h >> 24;
+    return h ^ (seed >> 16);
+}
+DA_HD uint64_t tie_pair_unmix(uint64_t h, uint64_t seed) {  // and its inverse
+    h ^= seed >> 16;
+    h ^= h >> 24;
+    h = (h * TIE_MUL_INV) & TIE_PAIR_MASK;
+    return h ^ (seed & TIE_PAIR_MASK);
+}
+DA_HD uint64_t tie_word_seeded(uint32_t id0, uint32_t id1, int idx, uint64_t seed) {
+    return (tie_pair_mix(((uint64_t)id1 << 24) | (uint64_t)id0, seed) << 7) | (uint64_t)tie_block_pos((uint32_t)idx, seed);
+}
+DA_HD uint64_t tie_word(uint32_t id0, uint32_t id1, int idx, uint64_t seed) {
+    return seed ? tie_word_seeded(id0, id1, idx, seed) : tie_word(id0, id1, idx);
+}
+// the rows of an entry from its tie word (seed 0: the reference's word), and its key index
+DA_HD void tie_word_rows(uint64_t tie, uint64_t seed, uint32_t &id0, uint32_t &id1) {
+    const uint64_t h = seed ? tie_pair_unmix(tie >> 7, seed) : tie >> 7;
+    id0 = (uint32_t)(h & 0xFFFFFFu);
+    id1 = (uint32_t)(h >> 24);
+}
+DA_HD int tie_word_idx(uint64_t tie, uint64_t seed) { return (int)(((uint32_t)tie & 0x7Fu) ^ tie_k7(seed)); }
+
 // ------------------------------------------------------------------------------------ qint / latency
 // qint_add(q0, q1, shift, false, sub) (state_opr.cc:8-29); all operations exact or single-rounded IEEE
 DA_HD void qint_add_pair(const RowInfo &a, const RowInfo &b, int shift, int sub, float &lo, float &hi, float &step) {

@@ -375,6 +375,8 @@ struct ChainDev {
 #endif
     unsigned long long st_qdiag[9];   // (phase-timer builds) [5] steps whose work list held > 32 groups, [6] the longest work list, [7] passes over the whole table (pick not known ahead), [8] work-list entries in all; group re-reads that found a stale bound below the floor / of clean groups with an excluded
                                       // best entry; [2],[3] scratch; [4] sum over the steps of the longest wave's re-read rounds
+    unsigned long long tie_seed;      // 0: ties are settled as the reference settles them; else the chain's seeded tie order (cmvm_core.h) -- a random restart.  Read by
+                                      // the SEEDED instantiations of the kernels only (last field: the offsets the others use are what they were)
 };
 
 __constant__ Log2Table c_log2;
@@ -476,10 +478,35 @@ struct Ctx {
     unsigned long long rword;  // k_iter_update: bound word of the best entry this step leaves untouched (0: none); the best entry of every block
     unsigned int *cn;          // written or re-evaluated whose bound word reaches it is appended to cl[(*cn)++] (fold_entry): together with that
     CandEntry *cl;             // entry they are all the next selection has to compare
+    unsigned long long seed;   // the chain's tie seed in the SEEDED instantiations (never 0 there), the constant 0 in the others
 };
 
+// ---- tie order of a chain.  SEEDED is a template parameter of every kernel that forms, compares or takes apart a tie word, as MANYCOL is of the
+// selection kernel: the unseeded instantiations are instruction for instruction what they were, a seeded chain pays one 48-bit multiply per word.
+// Every site goes through these four: a tie word formed one way and compared with one formed the other gives picks that are valid adder
+// graphs but not the maximum of the chain's order.
+template <bool SEEDED> __device__ __forceinline__ unsigned long long tie_of(uint32_t id0, uint32_t id1, int idx, unsigned long long seed) {
+    if constexpr (SEEDED)
+        return tie_word_seeded(id0, id1, idx, seed);
+    else
+        return tie_word(id0, id1, idx);
+}
+template <bool SEEDED> __device__ __forceinline__ void tie_rows(unsigned long long tie, unsigned long long seed, uint32_t &id0, uint32_t &id1) {
+    unsigned long long h = tie >> 7;
+    if constexpr (SEEDED) h = tie_pair_unmix(h, seed);
+    id0 = (uint32_t)(h & 0xFFFFFFu);
+    id1 = (uint32_t)(h >> 24);
+}
+// key index <-> position in the within-block order (the low byte of a block's `rank << 8 | position` maximum): an involution
+template <bool SEEDED> __device__ __forceinline__ uint32_t blk_pos(uint32_t k, unsigned long long seed) {
+    if constexpr (SEEDED)
+        return tie_block_pos(k, seed);
+    else
+        return k;
+}
+
 // launch_id: 2 * iteration for k_iter_select2, 2 * iteration + 1 for k_iter_update (only the low two bits are used)
-__device__ __forceinline__ Ctx make_ctx_raw(ChainDev *g, int launch_id) {
+template <bool SEEDED = false> __device__ __forceinline__ Ctx make_ctx_raw(ChainDev *g, int launch_id) {
     Ctx c;
     c.tomb = KEY_TOMB - (unsigned long long)(launch_id & 3);
     c.n_out = g->n_out;
@@ -500,11 +527,15 @@ __device__ __forceinline__ Ctx make_ctx_raw(ChainDev *g, int launch_id) {
     c.rword = 0;
     c.cn = nullptr;
     c.cl = nullptr;
+    if constexpr (SEEDED)
+        c.seed = g->tie_seed;
+    else
+        c.seed = 0;
     return c;
 }
 __device__ __forceinline__ void ctx_finish(Ctx &c) { c.windows = c.windows / WAVE ? c.windows / WAVE : 1; }  // after the fields are pinned
-__device__ __forceinline__ Ctx make_ctx(ChainDev *g, int launch_id) {
-    Ctx c = make_ctx_raw(g, launch_id);
+template <bool SEEDED = false> __device__ __forceinline__ Ctx make_ctx(ChainDev *g, int launch_id) {
+    Ctx c = make_ctx_raw<SEEDED>(g, launch_id);
     ctx_finish(c);
     return c;
 }
@@ -605,7 +636,7 @@ __device__ __forceinline__ DA_GLOBAL uint8_t *hidx_ptr(const Ctx &c) { return re
 // ONCE PER WORKGROUP: in the first thousands of steps of a chain hundreds of blocks are created and deleted per step, and one atomic each on the
 // same line of the chain descriptor serialises in the L2 at ~12 ns apiece -- behind which every later load of the issuing wave waits (vmcnt is
 // in-order): measured in round 6, k_iter_update of steps 0 - 2000 took 24.8 us for one chain where the late steps take 6.7.
-template <class CntFn>
+template <bool SEEDED = false, class CntFn>
 __device__ bool table_insert(const Ctx &c, uint32_t lo, uint32_t hi, const RowInfo &ra, const RowInfo &rb, CntFn cnt_of, unsigned long long *w_out = nullptr, bool tally = true) {
     int lane = lane_id();
     unsigned long long key = pack_pair(lo, hi);
@@ -623,19 +654,19 @@ __device__ bool table_insert(const Ctx &c, uint32_t lo, uint32_t hi, const RowIn
         if (n > 65535u) c.g->error = E_COUNT_OVERFLOW;
         cnt[k] = (uint16_t)n;
         uint32_t r = entry_rank(n, ov, dl, c.method);
-        unsigned long long cand = r ? (((unsigned long long)r << 8) | (unsigned)k) : 0ull;
+        unsigned long long cand = r ? (((unsigned long long)r << 8) | blk_pos<SEEDED>((unsigned)k, c.seed)) : 0ull;
         best = cand > best ? cand : best;
     }
     best = wave_max_u64(best);
-    if (w_out) *w_out = (best >> 8) ? bound_word((uint32_t)(best >> 8), tie_word(lo, hi, (int)(best & 0xFF))) : 0ull;
+    if (w_out) *w_out = (best >> 8) ? bound_word((uint32_t)(best >> 8), tie_of<SEEDED>(lo, hi, (int)blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed), c.seed)) : 0ull;
     if (lane == 0) {
-        uint32_t rank = (uint32_t)(best >> 8), idx = (uint32_t)(best & 0xFF);
+        uint32_t rank = (uint32_t)(best >> 8), idx = blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed);
         store_hdr(c, slot, ov, dl, rank, idx);
         c.hrank[slot] = rank;
         hidx_ptr(c)[slot] = (uint8_t)idx;
         if (rank) {
-            group_note(c, slot, 0ull, bound_word(rank, tie_word(lo, hi, (int)idx)));
-            fold_entry(c, rank, tie_word(lo, hi, (int)idx));
+            group_note(c, slot, 0ull, bound_word(rank, tie_of<SEEDED>(lo, hi, (int)idx, c.seed)));
+            fold_entry(c, rank, tie_of<SEEDED>(lo, hi, (int)idx, c.seed));
         }
         if (tally) atomicAdd(&c.g->n_live, 1u);  // no return value: fire-and-forget (the peak is sampled by the selection)
     }
@@ -644,11 +675,13 @@ __device__ bool table_insert(const Ctx &c, uint32_t lo, uint32_t hi, const RowIn
 
 // lane 0: publish the re-evaluated best key of a block (or delete the block when no count >= 2 is left)
 // bound word of a block's best entry as its header holds it
-__device__ __forceinline__ unsigned long long hdr_word(unsigned long long key, uint32_t rank, uint32_t idx) {
-    return rank ? bound_word(rank, tie_word((uint32_t)key, (uint32_t)(key >> 32), (int)idx)) : 0ull;
+template <bool SEEDED = false> __device__ __forceinline__ unsigned long long hdr_word(unsigned long long key, uint32_t rank, uint32_t idx, unsigned long long seed) {
+    return rank ? bound_word(rank, tie_of<SEEDED>((uint32_t)key, (uint32_t)(key >> 32), (int)idx, seed)) : 0ull;
 }
+// `best`: the block's maximum of (rank << 8 | position in the within-block order), 0 = nothing selectable
+template <bool SEEDED = false>
 __device__ __forceinline__ void block_commit(const Ctx &c, int slot, unsigned long long key, const BlkHdr &h, unsigned long long best, int alive, bool tally = true) {
-    const unsigned long long w_old = hdr_word(key, h.rank, h.idx);
+    const unsigned long long w_old = hdr_word<SEEDED>(key, h.rank, h.idx, c.seed);
     if (!alive) {
         c.hrank[slot] = 0;
         c.hkey[slot] = c.tomb;
@@ -656,18 +689,18 @@ __device__ __forceinline__ void block_commit(const Ctx &c, int slot, unsigned lo
         if (h.rank) group_note(c, slot, w_old, 0ull);
         return;
     }
-    const uint32_t rank = (uint32_t)(best >> 8), idx = (uint32_t)(best & 0xFF);
+    const uint32_t rank = (uint32_t)(best >> 8), idx = blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed);
     if (rank != h.rank) c.hrank[slot] = rank;
     if (rank != h.rank || idx != h.idx) store_best(c, slot, rank, idx);
     if (idx != h.idx) hidx_ptr(c)[slot] = (uint8_t)idx;
     if (rank != h.rank || (rank && idx != h.idx))
-        group_note(c, slot, w_old, rank ? bound_word(rank, tie_word((uint32_t)key, (uint32_t)(key >> 32), (int)idx)) : 0ull);
-    if (rank) fold_entry(c, rank, tie_word((uint32_t)key, (uint32_t)(key >> 32), (int)idx));  // changed or not: the block touches a row of the step
+        group_note(c, slot, w_old, rank ? bound_word(rank, tie_of<SEEDED>((uint32_t)key, (uint32_t)(key >> 32), (int)idx, c.seed)) : 0ull);
+    if (rank) fold_entry(c, rank, tie_of<SEEDED>((uint32_t)key, (uint32_t)(key >> 32), (int)idx, c.seed));  // changed or not: the block touches a row of the step
 }
 
 // Re-evaluate a block after its counts changed (new_cnt(k, old) -> new count); deletes it when no count >= 2.
 // Returns the bound word of the block's best entry afterwards (0: deleted, or nothing selectable); wave-uniform.
-template <class CntFn>
+template <bool SEEDED = false, class CntFn>
 __device__ unsigned long long table_update(const Ctx &c, int slot, unsigned long long key, CntFn new_cnt, bool tally = true, int *deleted = nullptr) {
     int lane = lane_id();
     const BlkHdr h = load_hdr(c, slot);
@@ -680,14 +713,14 @@ __device__ unsigned long long table_update(const Ctx &c, int slot, unsigned long
         if (n != old) cnt[k] = (uint16_t)n;
         alive |= n >= 2;
         uint32_t r = entry_rank(n, h.ov, h.dl, c.method);
-        unsigned long long cand = r ? (((unsigned long long)r << 8) | (unsigned)k) : 0ull;
+        unsigned long long cand = r ? (((unsigned long long)r << 8) | blk_pos<SEEDED>((unsigned)k, c.seed)) : 0ull;
         best = cand > best ? cand : best;
     }
     best = wave_max_u64(best);
     alive = __any(alive);
-    if (lane == 0) block_commit(c, slot, key, h, best, alive, tally);
+    if (lane == 0) block_commit<SEEDED>(c, slot, key, h, best, alive, tally);
     if (deleted) *deleted = !alive;
-    return alive && (best >> 8) ? bound_word((uint32_t)(best >> 8), tie_word((uint32_t)key, (uint32_t)(key >> 32), (int)(best & 0xFF))) : 0ull;
+    return alive && (best >> 8) ? bound_word((uint32_t)(best >> 8), tie_of<SEEDED>((uint32_t)key, (uint32_t)(key >> 32), (int)blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed), c.seed)) : 0ull;
 }
 
 // ------------------------------------------------------------------------------------------------ k_prepare
@@ -834,10 +867,10 @@ __device__ __forceinline__ bool wave_any_ge2(const uint32_t *cnt, int K) {
 
 // ------------------------------------------------------------------------------------------------ k_init_pairs
 // grid (ceil(n_pairs / 4), n_chains): one wave per initial row pair (i0 <= i1).
-template <class Cell> __global__ void __launch_bounds__(256) k_init_pairs(ChainDev *chains) {
+template <class Cell, bool SEEDED = false> __global__ void __launch_bounds__(256) k_init_pairs(ChainDev *chains) {
     ChainDev *g = &chains[blockIdx.y];
     if (g->method == M_DUMMY) return;
-    const Ctx c = make_ctx(g, 0);
+    const Ctx c = make_ctx<SEEDED>(g, 0);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *cnt = reinterpret_cast<uint32_t *>(smem) + (size_t)wave_id() * c.Kpad;
     long long n_in = g->n_in;
@@ -856,7 +889,7 @@ template <class Cell> __global__ void __launch_bounds__(256) k_init_pairs(ChainD
         if (lane_id() == 0) g->unknown_hit = 1;
         return;
     }
-    table_insert(c, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; });
+    table_insert<SEEDED>(c, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; });
 }
 
 // ================================================================================= k_iter_select2: the next pick, one step ahead
@@ -906,7 +939,8 @@ constexpr int QL_CAP = DA_CAND_CAP * 4;  // entries touching the pick's rows the
 // The table's best entry -- highest rank, then highest tie word -- by ONE WORKGROUP and a plain pass over the dense rank array: no bounds, nothing
 // written.  For the substitution block of a step whose pick is not known ahead (the first step of a chain; an overflowed candidate list): 4 bytes per
 // slot twice (8 + 8 MB for a 256x256 chain, once per chain).  rank 0: nothing selectable.  red_*: one LDS word per wave.  Ends with a block barrier.
-__device__ __forceinline__ void table_argmax_block(ChainDev *g, uint32_t &rank, unsigned long long &tie, uint32_t *red_rank, unsigned long long *red_tie) {
+template <bool SEEDED = false>
+__device__ __forceinline__ void table_argmax_block(ChainDev *g, unsigned long long seed, uint32_t &rank, unsigned long long &tie, uint32_t *red_rank, unsigned long long *red_tie) {
     const DA_GLOBAL uint32_t *hrank = (const DA_GLOBAL uint32_t *)g->hrank;
     const DA_GLOBAL unsigned long long *hkey = (const DA_GLOBAL unsigned long long *)g->hkey;
     const uint32_t C = g->C;
@@ -933,7 +967,7 @@ __device__ __forceinline__ void table_argmax_block(ChainDev *g, uint32_t &rank, 
                 if (r[q] == best) {
                     const uint32_t sl = 4 * i + (uint32_t)q;
                     const unsigned long long k = hkey[sl];
-                    const unsigned long long tw = tie_word((uint32_t)k, (uint32_t)(k >> 32), (int)hidx[sl]);
+                    const unsigned long long tw = tie_of<SEEDED>((uint32_t)k, (uint32_t)(k >> 32), (int)hidx[sl], seed);
                     bt = tw > bt ? tw : bt;
                 }
         }
@@ -973,20 +1007,21 @@ __device__ __forceinline__ bool resolve_pick(const DA_GLOBAL CandEntry *cl, unsi
     return true;
 }
 
-template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, int step) {
+template <class Cell, bool SEEDED = false> __device__ __forceinline__ void search_body(ChainDev *g, int step) {
     constexpr int NW = SEL2_THREADS / WAVE, GPL = MAX_GROUPS / SEL2_THREADS;  // waves; group bounds per lane
     constexpr int RKN = DA_SEL_RK;  // slots per lane of a group read that are held in registers (x 64 lanes: groups of up to 512 slots in one round trip)
     const int par = step & 1;
     int was_done = g->done, had_error = g->error, n_groups = g->n_groups;
     unsigned long long sp_word = g->spec[par ^ 1].word, sp_tie = g->spec[par ^ 1].tie;
     unsigned int cn_prev = g->c_n[par ^ 1];
-    Ctx c = make_ctx_raw(g, 2 * step);
+    Ctx c = make_ctx_raw<SEEDED>(g, 2 * step);
     const DA_GLOBAL da_u2 *rowoff = (const DA_GLOBAL da_u2 *)g->rowoff;
     const DA_GLOBAL CandEntry *cl_prev = (const DA_GLOBAL CandEntry *)&g->c_list[par ^ 1][0];
     DA_GLOBAL CandEntry *ll_out = (DA_GLOBAL CandEntry *)&g->l_list[par][0];
     pin_sgpr(was_done, had_error, n_groups, sp_word, sp_tie, cn_prev);
     pin_sgpr(c.gs_log2, c.cmask, c.hkey, c.hrank, c.grec, c.rows);
     pin_sgpr(rowoff, cl_prev, ll_out);
+    if constexpr (SEEDED) pin_sgpr(c.seed);
     if (was_done || had_error != E_OK) return;  // (the substitution block stops the chain)
     __shared__ unsigned long long q_floor, q_red_tie[NW], q_ub[GPL][SEL2_THREADS];
     __shared__ uint32_t q_work[MAX_GROUPS];  // groups still to be read after round 0: index into q_ub | dirty << 31
@@ -1005,10 +1040,7 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
     bool from_spec;
     const bool fast = resolve_pick(cl_prev, sp_word, sp_tie, cn_prev, pk_tie, from_spec);
     uint32_t exA = ROW_NONE, exB = ROW_NONE;  // rows whose entries the pass leaves out
-    if (fast) {
-        exA = (uint32_t)((pk_tie >> 7) & 0xFFFFFFu);
-        exB = (uint32_t)(pk_tie >> 31);
-    }
+    if (fast) tie_rows<SEEDED>(pk_tie, c.seed, exA, exB);
     unsigned int rescans = 0;
 #ifdef DA_PHASE_TIMERS
     unsigned int q_stale = 0, q_touch = 0, q_rounds = 0;
@@ -1029,7 +1061,8 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
         unsigned long long nt = 0;
         // returns the entry's bound word if it counts towards the floor, else 0; fl = the floor at the time (entries of the excluded rows are listed from there on)
         auto offer = [&](uint32_t r, unsigned long long tw, unsigned long long fl, bool list) -> unsigned long long {
-            const uint32_t i0 = (uint32_t)((tw >> 7) & 0xFFFFFFu), i1 = (uint32_t)(tw >> 31);
+            uint32_t i0, i1;
+            tie_rows<SEEDED>(tw, c.seed, i0, i1);
             const bool t0 = i0 == exA || i0 == exB, t1 = i1 == exA || i1 == exB;
             if (!(t0 || t1)) {
                 if (r > nr || (r == nr && tw > nt)) {
@@ -1143,7 +1176,7 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
                         for (int v = 1; v < RKN; ++v) r = u == v ? rk[v] : r;
                         const uint32_t sl = base + (uint32_t)(lane + u * WAVE);
                         const unsigned long long k = c.hkey[sl];
-                        const unsigned long long tw = tie_word((uint32_t)k, (uint32_t)(k >> 32), (int)hidx[sl]);
+                        const unsigned long long tw = tie_of<SEEDED>((uint32_t)k, (uint32_t)(k >> 32), (int)hidx[sl], c.seed);
                         if (r == grank) gt = tw > gt ? tw : gt;
                         lw = max(lw, offer(r, tw, fl, pass != 0));
                     }
@@ -1152,7 +1185,7 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
                     const uint32_t r2 = c.hrank[base + o];
                     if (r2 >= thr) {
                         const unsigned long long k2 = c.hkey[base + o];
-                        const unsigned long long tw = tie_word((uint32_t)k2, (uint32_t)(k2 >> 32), (int)hidx[base + o]);
+                        const unsigned long long tw = tie_of<SEEDED>((uint32_t)k2, (uint32_t)(k2 >> 32), (int)hidx[base + o], c.seed);
                         if (r2 == grank) gt = tw > gt ? tw : gt;
                         lw = max(lw, offer(r2, tw, fl, pass != 0));
                     }
@@ -1238,7 +1271,12 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
         const uint32_t wnr = wave_max_u32(nr);
         const unsigned long long wnt = wave_max_u64(nr == wnr ? nt : 0ull);
         // every wave fetches list references and records of ITS candidate's rows now (in flight across the reduction)
-        const uint32_t cA = wnr ? (uint32_t)((wnt >> 7) & 0xFFFFFFu) : 0u, cB = wnr ? (uint32_t)(wnt >> 31) : 0u;
+        uint32_t cA = 0u, cB = 0u;
+        if constexpr (SEEDED) {
+            if (wnr) tie_rows<SEEDED>(wnt, c.seed, cA, cB);
+        } else {
+            cA = wnr ? (uint32_t)((wnt >> 7) & 0xFFFFFFu) : 0u, cB = wnr ? (uint32_t)(wnt >> 31) : 0u;
+        }
         const RowInfo cand_ra = load_row(c.rows, cA), cand_rb = load_row(c.rows, cB);
         const da_u2 cand_refA = rowoff[cA], cand_refB = rowoff[cB];
         if (lane == 0) {
@@ -1266,8 +1304,7 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
                 if (lane == 0 && rescans) atomicAdd(&g->st_rescans, (unsigned long long)rescans);
                 return;  // the table holds nothing selectable: the chain ends
             }
-            exA = (uint32_t)((best_tie >> 7) & 0xFFFFFFu);
-            exB = (uint32_t)(best_tie >> 31);
+            tie_rows<SEEDED>(best_tie, c.seed, exA, exB);
             __threadfence();  // the bounds this pass tightened are re-read by the next one: stores complete, this CU's L1 dropped
             __syncthreads();
         } else {
@@ -1343,7 +1380,8 @@ template <class Cell> __device__ __forceinline__ void search_body(ChainDev *g, i
 // that end the chunks of pass 1 order it before pass 2, which reads the entries back) --, the per-column arrays that hold values of at most n_out
 // are 16-bit, and the list length of a matched column is read from `collen` at the hit (it grows only after pass 1).
 // Returns 1 when the chain is (or just became) finished.
-template <class Cell, bool SHARDED = false, bool MANYCOL = false> __device__ __forceinline__ int pick_body(ChainDev *g, unsigned int *n_done, int step) {
+template <class Cell, bool SHARDED = false, bool MANYCOL = false, bool SEEDED = false> __device__ __forceinline__ int pick_body(ChainDev *g, unsigned int *n_done, int step) {
+    static_assert(!(SHARDED && SEEDED), "column-sharded chains keep the reference's tie order");
     using O = CellOps<Cell>;
     using F = RowFmt<Cell>;
     using Entry = typename F::Entry;
@@ -1361,7 +1399,7 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false> __device__ __f
     uint32_t sp_ax = g->spec[par ^ 1].refA.x, sp_ay = g->spec[par ^ 1].refA.y, sp_bx = g->spec[par ^ 1].refB.x, sp_by = g->spec[par ^ 1].refB.y;
     float sp_ra0 = g->spec[par ^ 1].ra.lo, sp_ra1 = g->spec[par ^ 1].ra.hi, sp_ra2 = g->spec[par ^ 1].ra.step, sp_ra3 = g->spec[par ^ 1].ra.lat;
     float sp_rb0 = g->spec[par ^ 1].rb.lo, sp_rb1 = g->spec[par ^ 1].rb.hi, sp_rb2 = g->spec[par ^ 1].rb.step, sp_rb3 = g->spec[par ^ 1].rb.lat;
-    Ctx c = make_ctx_raw(g, 2 * iter);
+    Ctx c = make_ctx_raw<SEEDED>(g, 2 * iter);
     DA_GLOBAL int *collen = (DA_GLOBAL int *)g->collen;
     DA_GLOBAL da_u2 *rowoff = (DA_GLOBAL da_u2 *)g->rowoff;
     DA_GLOBAL Entry *rl = (DA_GLOBAL Entry *)g->rlist;
@@ -1380,6 +1418,7 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false> __device__ __f
     pin_sgpr(c.n_out, c.n_bits, c.K, c.Kpad, c.rows);
     pin_sgpr(collen, rowoff, rl, mA, mB, mcol, collist, cmap, colbits, pl_ids, plist, picks, sp_cnt);
     if constexpr (SHARDED) pin_sgpr(cs_slab, cs_flags);
+    if constexpr (SEEDED) pin_sgpr(c.seed);
     const int n_out = c.n_out, Kpad = c.Kpad, nb = c.n_bits;
     // column-sharded chain (cmvm_shard.h): a rank whose chain stops (finished, or an error) still hands out the flag buffer of the step -- zero
     // flags and the status trailer {1, capacity error?, other error?} -- written here, on the device: the host does not read the descriptor
@@ -1449,7 +1488,8 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false> __device__ __f
     unsigned long long best_tie;
     bool from_spec;
     const bool fast = resolve_pick(cl_prev, sp_word, sp_tie, cn_prev, best_tie, from_spec);
-    uint32_t A = (uint32_t)((best_tie >> 7) & 0xFFFFFFu), B = (uint32_t)(best_tie >> 31);
+    uint32_t A, B;
+    tie_rows<SEEDED>(best_tie, c.seed, A, B);
     da_u2 refA = da_u2{sp_ax, sp_ay}, refB = da_u2{sp_bx, sp_by};
     RowInfo ra = RowInfo{sp_ra0, sp_ra1, sp_ra2, sp_ra3}, rb = RowInfo{sp_rb0, sp_rb1, sp_rb2, sp_rb3};
     if (fast && !from_spec) {  // (block-uniform) a listed entry won: its rows' list references and records (one round trip, broadcast loads)
@@ -1489,10 +1529,9 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false> __device__ __f
         // plain pass over the rank array -- nothing is written, no bound is read, and nothing is awaited from the search block of this launch, which
         // finds the same entry through the bounds for its own purpose (HIP promises nothing about the order in which workgroups are dispatched)
         uint32_t r0;
-        table_argmax_block(g, r0, best_tie, s_am_rank, s_am_tie);
+        table_argmax_block<SEEDED>(g, c.seed, r0, best_tie, s_am_rank, s_am_tie);
         pk_word = r0 ? bound_word(r0, best_tie) : 0ull;
-        A = (uint32_t)((best_tie >> 7) & 0xFFFFFFu);
-        B = (uint32_t)(best_tie >> 31);
+        tie_rows<SEEDED>(best_tie, c.seed, A, B);
         if (pk_word) {
             refA = rowoff[A];
             refB = rowoff[B];
@@ -1513,7 +1552,7 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false> __device__ __f
         shard_stop(pk_word != 0 ? E_ROW_CAPACITY : E_OK);
         return 1;
     }
-    const int idx = (int)(best_tie & 0x7F);
+    const int idx = (int)blk_pos<SEEDED>((uint32_t)(best_tie & 0x7F), c.seed);
     int shift, sub;
     key_decode(idx, nb, shift, sub);
     const bool same = A == B;
@@ -1800,7 +1839,7 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false> __device__ __f
 #ifndef DA_SEL2_WAVES
 #define DA_SEL2_WAVES 4  // wavefronts per SIMD the register budget of k_iter_select2 is capped for (measured 4 .. 8: the spills of 5 and more cost more than the smaller footprint gains)
 #endif
-template <class Cell, bool SHARDED = false, bool MANYCOL = false> __global__ void __launch_bounds__(SEL2_THREADS) __attribute__((amdgpu_waves_per_eu(DA_SEL2_WAVES, DA_SEL2_WAVES))) k_iter_select2(ChainDev *chains, int n_chains, unsigned int *n_done, int step) {
+template <class Cell, bool SHARDED = false, bool MANYCOL = false, bool SEEDED = false> __global__ void __launch_bounds__(SEL2_THREADS) __attribute__((amdgpu_waves_per_eu(DA_SEL2_WAVES, DA_SEL2_WAVES))) k_iter_select2(ChainDev *chains, int n_chains, unsigned int *n_done, int step) {
     if ((int)blockIdx.x >= n_chains) return;
 #ifdef DA_STEP_CLOCKS
     {
@@ -1822,9 +1861,9 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false> __global__ voi
     }
 #endif
     if (blockIdx.y == 0)
-        search_body<Cell>(&chains[blockIdx.x], step);
+        search_body<Cell, SEEDED>(&chains[blockIdx.x], step);
     else
-        (void)pick_body<Cell, SHARDED, MANYCOL>(&chains[blockIdx.x], n_done, step);
+        (void)pick_body<Cell, SHARDED, MANYCOL, SEEDED>(&chains[blockIdx.x], n_done, step);
 #ifdef DA_STEP_CLOCKS
     __syncthreads();
     if (threadIdx.x == 0) CLK_MARK(&chains[blockIdx.x], step & 1, 1, false);
@@ -1889,14 +1928,14 @@ template <class Cell> struct UpdStep {
     const DA_GLOBAL unsigned long long *plist;
 };
 // ONE round trip: every descriptor field an update worker needs, pinned before the first branch (pin_sgpr)
-template <class Cell> __device__ __forceinline__ UpdStep<Cell> load_upd_step(ChainDev *gq) {
+template <class Cell, bool SEEDED = false> __device__ __forceinline__ UpdStep<Cell> load_upd_step(ChainDev *gq) {
     using Entry = typename RowFmt<Cell>::Entry;
     UpdStep<Cell> u;
     int iter = gq->iter;
     u.done = gq->done, u.n_partners = gq->n_partners, u.m = gq->m, u.n_in = gq->n_in;
     u.A = gq->A, u.B = gq->B, u.Nw = gq->Nw;
     u.shift = gq->pk_shift, u.sub = gq->pk_sub;
-    u.c = make_ctx_raw(gq, 2 * iter - 1);
+    u.c = make_ctx_raw<SEEDED>(gq, 2 * iter - 1);
     // the step being applied is iter - 1 (the selection has counted it): its search left the best entry the step does not touch in
     // spec[(iter - 1) & 1]; the best entry of every block this launch writes that reaches it goes to c_list[(iter - 1) & 1] (fold_entry)
     u.c.rword = gq->spec[(iter - 1) & 1].word;
@@ -1910,6 +1949,7 @@ template <class Cell> __device__ __forceinline__ UpdStep<Cell> load_upd_step(Cha
     pin_sgpr(u.done, u.n_partners, iter, u.m, u.n_in, u.A, u.B, u.Nw, u.shift, u.sub, u.mcol, u.mA, u.cmap, u.rl, u.plist);
     pin_sgpr(u.c.n_out, u.c.n_bits, u.c.K, u.c.Kpad, u.c.method, u.c.gs_log2, u.c.pb_log2, u.c.cmask, u.c.windows, u.c.hkey, u.c.hrank, u.c.hblk, u.c.grec, u.c.rows);
     pin_sgpr(u.c.rword, u.c.cn, u.c.cl);
+    if constexpr (SEEDED) pin_sgpr(u.c.seed);
     u.c.tomb = KEY_TOMB - (unsigned long long)((2 * iter - 1) & 3);
     ctx_finish(u.c);
     return u;
@@ -1947,7 +1987,7 @@ template <class Cell> __device__ __forceinline__ void copy_handoff(const UpdStep
 // partner, `rnew` the record of the new row.
 // STATS: tally the blocks found / created / deleted (benchmark instrumentation and the "peak pair blocks" statistic, DA4ML_HIP_STATS=1); the ballots, population
 // counts and the scalar registers of the three counters are 1.8 % of the batch's step (measured: 27.9 -> 27.5 us, one chain 19.5 -> 19.0), so the product runs without them
-template <class Cell, bool STATS>
+template <class Cell, bool STATS, bool SEEDED = false>
 __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell> &u, const UpdLds<Cell> &s, int first, int stride, int limit, unsigned long long ref_next,
                                                 const RowInfo &rnew, unsigned int &found, unsigned int &inserts, unsigned int &deletes) {
     using F = RowFmt<Cell>;
@@ -2116,15 +2156,15 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     if (n0 != o0 || n1 != o1) reinterpret_cast<DA_GLOBAL uint32_t *>(blk_ptr(c, sX) + 16)[j] = (n0 & 0xFFFFu) | (n1 << 16);
                     alive |= (n0 >= 2u) | (n1 >= 2u);
                     const uint32_t r0 = entry_rank(n0, ov, dl, c.method), r1 = entry_rank(n1, ov, dl, c.method);
-                    const unsigned long long c0 = r0 ? (((unsigned long long)r0 << 8) | (unsigned)(2 * j)) : 0ull;
-                    const unsigned long long c1 = r1 ? (((unsigned long long)r1 << 8) | (unsigned)(2 * j + 1)) : 0ull;
+                    const unsigned long long c0 = r0 ? (((unsigned long long)r0 << 8) | blk_pos<SEEDED>((unsigned)(2 * j), c.seed)) : 0ull;
+                    const unsigned long long c1 = r1 ? (((unsigned long long)r1 << 8) | blk_pos<SEEDED>((unsigned)(2 * j + 1), c.seed)) : 0ull;
                     best = c0 > best ? c0 : best;
                     best = c1 > best ? c1 : best;
                 }
             }
             best = part_row_max_u64<HL>(best);  // all lanes take part (the DPP source lanes must be active); every lane of a block's HL holds its result
             const bool any_alive = (((uint32_t)(__ballot(alive != 0) >> (qsh + HL * half)) & HMASK) != 0);
-            if (has && hl == HL - 1) block_commit(c, sX, keyX, BlkHdr{ov, dl, (uint32_t)hdX.z, (uint32_t)hdX.w}, best, any_alive, false);
+            if (has && hl == HL - 1) block_commit<SEEDED>(c, sX, keyX, BlkHdr{ov, dl, (uint32_t)hdX.z, (uint32_t)hdX.w}, best, any_alive, false);
             if constexpr (STATS) deletes += (unsigned)__popcll(__ballot(has && hl == HL - 1 && !any_alive));  // (wave-uniform: the blocks this pass deleted, tallied once per workgroup)
         }
         UPD_TIMER_MARK(3)  // block updates
@@ -2183,8 +2223,8 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     if ((n0 | n1) > 65535u) c.g->error = E_COUNT_OVERFLOW;
                     reinterpret_cast<DA_GLOBAL uint32_t *>(blk_ptr(c, nslot) + 16)[j] = (n0 & 0xFFFFu) | (n1 << 16);
                     const uint32_t r0 = entry_rank(n0, ovn, dln, c.method), r1 = entry_rank(n1, ovn, dln, c.method);
-                    const unsigned long long c0 = r0 ? (((unsigned long long)r0 << 8) | (unsigned)(2 * j)) : 0ull;
-                    const unsigned long long c1 = r1 ? (((unsigned long long)r1 << 8) | (unsigned)(2 * j + 1)) : 0ull;
+                    const unsigned long long c0 = r0 ? (((unsigned long long)r0 << 8) | blk_pos<SEEDED>((unsigned)(2 * j), c.seed)) : 0ull;
+                    const unsigned long long c1 = r1 ? (((unsigned long long)r1 << 8) | blk_pos<SEEDED>((unsigned)(2 * j + 1), c.seed)) : 0ull;
                     bestn = c0 > bestn ? c0 : bestn;
                     bestn = c1 > bestn ? c1 : bestn;
                 }
@@ -2192,13 +2232,13 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
             bestn = part_row_max_u64<8>(bestn);  // (eight lanes, then the two halves of the group)
             if constexpr (QG == 16) bestn = dpp_max_u64<0x140, 0xF>(bestn);  // row_mirror: lane i <-> 15 - i
             if (made && l == QG - 1) {
-                const uint32_t rank = (uint32_t)(bestn >> 8), bidx = (uint32_t)(bestn & 0xFF);
+                const uint32_t rank = (uint32_t)(bestn >> 8), bidx = blk_pos<SEEDED>((uint32_t)(bestn & 0xFF), c.seed);
                 store_hdr(c, nslot, ovn, dln, rank, bidx);
                 c.hrank[nslot] = rank;
                 hidx_ptr(c)[nslot] = (uint8_t)bidx;
                 if (rank) {
-                    group_note(c, nslot, 0ull, bound_word(rank, tie_word(pr, Nw, (int)bidx)));
-                    fold_entry(c, rank, tie_word(pr, Nw, (int)bidx));
+                    group_note(c, nslot, 0ull, bound_word(rank, tie_of<SEEDED>(pr, Nw, (int)bidx, c.seed)));
+                    fold_entry(c, rank, tie_of<SEEDED>(pr, Nw, (int)bidx, c.seed));
                 }
             }
             if constexpr (STATS) inserts += (unsigned)__popcll(__ballot(made && l == 0));
@@ -2219,7 +2259,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const int slot = table_find_from(c, pack_pair(lo, hi), hash_pair(lo, hi), 1);
                     if (slot >= 0) {
                         int gone = 0;
-                        table_update(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdA[k]; }, false, &gone);
+                        table_update<SEEDED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdA[k]; }, false, &gone);
                         if constexpr (STATS) deletes += (unsigned)gone, ++found;
                     }
                 }
@@ -2228,12 +2268,12 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const int slot = table_find_from(c, pack_pair(lo, hi), hash_pair(lo, hi), 1);
                     if (slot >= 0) {
                         int gone = 0;
-                        table_update(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdB[k]; }, false, &gone);
+                        table_update<SEEDED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdB[k]; }, false, &gone);
                         if constexpr (STATS) deletes += (unsigned)gone, ++found;
                     }
                 }
                 if (rnewb) {
-                    table_insert(c, rpr, Nw, load_row(c.rows, rpr), rnew, [&](int k) { return rcN[k]; }, nullptr, false);
+                    table_insert<SEEDED>(c, rpr, Nw, load_row(c.rows, rpr), rnew, [&](int k) { return rcN[k]; }, nullptr, false);
                     if constexpr (STATS) ++inserts;
                 }
             }
@@ -2251,7 +2291,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
 // Two workgroups per chain share the work, one pair per wavefront and ONE turn each (find -> re-count / create: the longest dependent chain
 // of this kernel; with all six in one workgroup of four waves it took two turns): part 0 the four pairs with A, part 1 (B,N), (N,N) and the
 // listed entries.
-template <class Cell> __device__ __forceinline__ void special_pairs(ChainDev *gq, const UpdStep<Cell> &u, int part) {
+template <class Cell, bool SEEDED = false> __device__ __forceinline__ void special_pairs(ChainDev *gq, const UpdStep<Cell> &u, int part) {
     const Ctx &c = u.c;
     const uint32_t A = u.A, B = u.B, Nw = u.Nw;
     const bool same = A == B;
@@ -2276,13 +2316,13 @@ template <class Cell> __device__ __forceinline__ void special_pairs(ChainDev *gq
         const int slot = existed ? table_find(c, key, hash_pair(lo, hi)) : -1;
         unsigned long long w = 0;
         if (slot >= 0)
-            w = table_update(c, slot, key, [&](int k, uint32_t) { return cnt[k]; });
+            w = table_update<SEEDED>(c, slot, key, [&](int k, uint32_t) { return cnt[k]; });
         else {
             int f = 0;
             for (int k = lane; k < c.K; k += WAVE) f |= cnt[k] >= 2u;
             if (__any(f)) {
                 const RowInfo xa = pick_row(lo == Nw, rn, pick_row(lo == A, ra, rb)), xb = pick_row(hi == Nw, rn, pick_row(hi == A, ra, rb));
-                table_insert(c, lo, hi, xa, xb, [&](int k) { return cnt[k]; }, &w);
+                table_insert<SEEDED>(c, lo, hi, xa, xb, [&](int k) { return cnt[k]; }, &w);
             }
         }
         (void)w;  // (both paths have passed the block's best entry to fold_entry)
@@ -2297,7 +2337,8 @@ template <class Cell> __device__ __forceinline__ void special_pairs(ChainDev *gq
         const int cbw = gq->cb_words;
         for (int e = (wave_id() + 2) % UPD_WAVES; e < nl; e += UPD_WAVES) {  // (waves 2 and 3 first: 0 and 1 had a pair)
             const unsigned long long tw = ll[e].tie;
-            const uint32_t i0 = (uint32_t)((tw >> 7) & 0xFFFFFFu), i1 = (uint32_t)(tw >> 31);
+            uint32_t i0, i1;
+            tie_rows<SEEDED>(tw, c.seed, i0, i1);
             const uint32_t r = (i0 == A || i0 == B) ? i1 : i0;
             int hit = 0;
             for (int k = lane; k < u.m; k += WAVE) hit |= (int)((colbits[(size_t)u.mcol[k] * cbw + (r >> 5)] >> (r & 31)) & 1u);
@@ -2308,17 +2349,17 @@ template <class Cell> __device__ __forceinline__ void special_pairs(ChainDev *gq
 
 // update_body: the partner rows [block_y * NWV * QN + ..., stride grid_y * NWV * QN) of chain `gq`'s current step, by a
 // workgroup of NWV wavefronts (k_iter_update: 256-thread blocks, grid = chains x blocks per chain).
-template <class Cell, int NWV, bool STATS>
+template <class Cell, int NWV, bool STATS, bool SEEDED = false>
 __device__ __forceinline__ void update_body(ChainDev *gq, bool in_range, int block_y, int grid_y) {
     constexpr int NTHR = NWV * WAVE;
     // Grid (chains padded to a multiple of 8, blocks per chain): the chain index is the FAST grid dimension.  Workgroups go to
     // the XCDs round-robin by their linear id, so all blocks of chain c -- and block c of k_iter_select, which has the same
     // linear id modulo 8 -- run on XCD c mod 8: the table lines, bounds and lists of a chain stay in ONE of the eight
     // non-coherent L2s instead of being spread over all of them.
-    const UpdStep<Cell> u = load_upd_step<Cell>(gq);
+    const UpdStep<Cell> u = load_upd_step<Cell, SEEDED>(gq);
     if (!in_range || u.done) return;
     if (block_y >= grid_y - 2) {  // the last two blocks of a chain: the six blocks of the pairs among {A, B, new row}
-        special_pairs<Cell>(gq, u, block_y - (grid_y - 2));
+        special_pairs<Cell, SEEDED>(gq, u, block_y - (grid_y - 2));
         return;
     }
     grid_y -= 2;
@@ -2340,7 +2381,7 @@ __device__ __forceinline__ void update_body(ChainDev *gq, bool in_range, int blo
     copy_handoff<Cell>(u, s, tid, NTHR);  // one pass, one barrier (the column map arrives ready-made)
     __syncthreads();
     unsigned int found = 0, inserts = 0, deletes = 0;
-    update_partners<Cell, STATS>(gq, u, s, gw * QN, total_waves * QN, u.n_partners, ref0, rnew, found, inserts, deletes);
+    update_partners<Cell, STATS, SEEDED>(gq, u, s, gw * QN, total_waves * QN, u.n_partners, ref0, rnew, found, inserts, deletes);
     if constexpr (!STATS) return;
     // statistics: summed per block in LDS, then ONE pair of device atomics per block.  (Four atomics per wave on one line
     // of the chain descriptor -- 640 per chain and launch, from all XCDs -- serialise at ~12 ns each and every launch had
@@ -2357,7 +2398,7 @@ __device__ __forceinline__ void update_body(ChainDev *gq, bool in_range, int blo
         if (s_stat[1] != s_stat[2]) atomicAdd(&gq->n_live, s_stat[1] - s_stat[2]);  // blocks created less blocks deleted by this workgroup (modulo 2^32)
     }
 }
-template <class Cell, bool STATS>
+template <class Cell, bool STATS, bool SEEDED = false>
 __global__ void __launch_bounds__(UPD_THREADS, DA_UPD_OCC) __attribute__((amdgpu_num_sgpr(DA_UPD_SGPRS))) k_iter_update(ChainDev *chains, int n_chains) {
     // Grid (chains padded to a multiple of 8, blocks per chain): the chain index is the FAST grid dimension (see update_body)
 #ifdef DA_STEP_CLOCKS
@@ -2366,7 +2407,7 @@ __global__ void __launch_bounds__(UPD_THREADS, DA_UPD_OCC) __attribute__((amdgpu
     const int clk_par = (gk->iter - 1) & 1;
     if (clk_on && threadIdx.x == 0) CLK_MARK(gk, clk_par, 2, true);
 #endif
-    update_body<Cell, UPD_WAVES, STATS>(&chains[(int)blockIdx.x < n_chains ? blockIdx.x : 0], (int)blockIdx.x < n_chains, (int)blockIdx.y, (int)gridDim.y);  // clamped: the descriptor read is unconditional
+    update_body<Cell, UPD_WAVES, STATS, SEEDED>(&chains[(int)blockIdx.x < n_chains ? blockIdx.x : 0], (int)blockIdx.x < n_chains, (int)blockIdx.y, (int)gridDim.y);  // clamped: the descriptor read is unconditional
 #ifdef DA_STEP_CLOCKS
     __syncthreads();
     if (clk_on && threadIdx.x == 0) CLK_MARK(gk, clk_par, 3, false);

@@ -726,7 +726,7 @@ std::vector<PipeResult> solve_batch_unique(Backend &be, const std::vector<Proble
 bool same_problem(const Problem &a, const Problem &b) {
     const SolveOptions &x = a.opt, &y = b.opt;
     if (a.n_in != b.n_in || a.n_out != b.n_out || x.hard_dc != y.hard_dc || x.decompose_dc != y.decompose_dc || x.adder_size != y.adder_size ||
-        x.carry_size != y.carry_size || x.search_all != y.search_all || x.method0 != y.method0 || x.method1 != y.method1 ||
+        x.carry_size != y.carry_size || x.search_all != y.search_all || x.seed != y.seed || x.method0 != y.method0 || x.method1 != y.method1 ||
         x.qints.size() != y.qints.size() || x.lats.size() != y.lats.size())
         return false;
     // bitwise comparisons: anything that is not literally the same input is simply solved again
@@ -767,13 +767,16 @@ uint64_t problem_hash(const Problem &p) {
     mix(p.kernel, sizeof(float) * (size_t)p.n_in * p.n_out);
     if (!p.opt.qints.empty()) mix(p.opt.qints.data(), sizeof(QInt) * p.opt.qints.size());
     if (!p.opt.lats.empty()) mix(p.opt.lats.data(), sizeof(float) * p.opt.lats.size());
+    const uint32_t seed_words[2] = {(uint32_t)p.opt.seed, (uint32_t)(p.opt.seed >> 32)};
+    mix(seed_words, sizeof seed_words);  // (the restarts of one matrix differ in nothing else)
     return h;
 }
 }  // namespace
 
-// Identical problems of a batch (same matrix, options, intervals and latencies -- the tracer's loop over the row
+// Identical problems of a batch (same matrix, options, tie seed, intervals and latencies -- the tracer's loop over the row
 // vectors of a traced tensor, reference trace/fixed_variable_array.py:368-371, produces many) are solved once and the
-// result is copied.  The solver is deterministic, so this cannot change any result.
+// result is copied.  The solver is deterministic for a given tie seed, so this cannot change any result.
+// (Problems that differ in the seed only -- the restarts of one matrix -- are solved each, and share the Stage1 of their matrix below.)
 std::vector<PipeResult> solve_batch(Backend &be, const std::vector<Problem> &problems, std::vector<ChainStats> *stats) {
     const size_t n = problems.size();
     std::vector<int> rep(n);
@@ -911,7 +914,7 @@ std::vector<PipeResult> solve_batch_unique(Backend &be, const std::vector<Proble
                     c.allowed = c.hard_dc + s.minlat;
                     c.phase = Candidate::NEED_STAGE0;
                 } else if (!minlat_queued[c.problem]) {
-                    // minimal_latency(): adder trees straight from the CSD digits (api.cc:11-26)
+                    // minimal_latency(): adder trees straight from the CSD digits (api.cc:11-26); no greedy loop, so no tie seed
                     jobs.push_back(ChainJob{p.kernel, p.n_in, p.n_out, M_DUMMY, s.qints.data(), s.lats.data(), p.opt.adder_size, p.opt.carry_size});
                     owners.push_back(Pending{(int)ci, 0, c.problem});
                     minlat_queued[c.problem] = 1;
@@ -920,10 +923,10 @@ std::vector<PipeResult> solve_batch_unique(Backend &be, const std::vector<Proble
                     continue;
             }
             if (c.phase == Candidate::NEED_STAGE0) {
-                jobs.push_back(ChainJob{c.m0.data(), p.n_in, p.n_out, parse_method(c.method0), s.qints.data(), s.lats.data(), p.opt.adder_size, p.opt.carry_size});
+                jobs.push_back(ChainJob{c.m0.data(), p.n_in, p.n_out, parse_method(c.method0), s.qints.data(), s.lats.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed});
                 owners.push_back(Pending{(int)ci, 1, c.problem});
             } else if (c.phase == Candidate::NEED_STAGE1) {
-                jobs.push_back(ChainJob{c.m1.data(), p.n_out, p.n_out, parse_method(c.method1), c.q_mid.data(), c.lat_mid.data(), p.opt.adder_size, p.opt.carry_size});
+                jobs.push_back(ChainJob{c.m1.data(), p.n_out, p.n_out, parse_method(c.method1), c.q_mid.data(), c.lat_mid.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed});
                 owners.push_back(Pending{(int)ci, 2, c.problem});
             }
         }

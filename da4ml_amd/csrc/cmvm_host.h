@@ -52,6 +52,7 @@ struct ChainJob {
     const QInt *qints = nullptr;  // [n_in]
     const float *lats = nullptr;  // [n_in]
     int adder_size = -1, carry_size = -1;
+    uint64_t tie_seed = 0;  // 0: equal scores are settled as the reference settles them; else by the seeded tie order of cmvm_core.h (a random restart of the greedy search)
 };
 struct ChainOut {
     int error = E_OK;
@@ -89,6 +90,7 @@ struct SolveOptions {
     std::vector<float> lats;   // empty -> 0
     int adder_size = -1, carry_size = -1;
     bool search_all = true;
+    uint64_t seed = 0;  // tie seed of every greedy chain of the problem (0: the reference's result)
 };
 
 int parse_method(const std::string &name);  // da::Method or -1

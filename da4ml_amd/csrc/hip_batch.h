@@ -28,16 +28,16 @@ struct HipBackend::Impl::Batch {
     std::vector<Geometry> geo;
     std::vector<size_t> a_off;  // of every chain in the arena
     size_t arena_bytes = 0, budget = 0, free_b = 0;
-    std::vector<int> order;  // descriptor s of the device is chain order[s] of the call: narrow chains first, and of a width those of the regular selection carve first
+    std::vector<int> order;  // descriptor s of the device is chain order[s] of the call: chains of the reference's tie order first, of those the narrow ones first, and of a width those of the regular selection carve first
     std::vector<char> manycol;  // per chain: it runs the many-column instantiation of k_iter_select2 (sel2_manycol)
-    static constexpr int N_VAR = 4;  // kernel variants of a batch: 2 * wide + manycol
-    int variant(int i) const { return 2 * (int)geo[i].wide + (int)manycol[i]; }
+    static constexpr int N_VAR = 8;  // kernel variants of a batch: 4 * seeded + 2 * wide + manycol (a batch of restarts mixes tie orders: restart 0 has the reference's)
+    int variant(int i) const { return 4 * (int)(jobs[i].tie_seed != 0) + 2 * (int)geo[i].wide + (int)manycol[i]; }
     struct Range {
         int first, count;
-        bool wide, manycol;
+        bool wide, manycol, seeded;
     } ranges[N_VAR];
-    size_t sel_lds[N_VAR] = {0, 0, 0, 0}, upd_lds[N_VAR] = {0, 0, 0, 0};  // per variant: dynamic LDS of the loop's kernels, k_iter_update blocks per chain
-    int upd_blocks[N_VAR] = {1, 1, 1, 1};
+    size_t sel_lds[N_VAR] = {}, upd_lds[N_VAR] = {};  // per variant: dynamic LDS of the loop's kernels, k_iter_update blocks per chain
+    int upd_blocks[N_VAR] = {1, 1, 1, 1, 1, 1, 1, 1};
     EventGuard events;  // declared before anything greedy_loop declares: destroyed after its streams have been drained, and after extract has read the clocks
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> sample_ev;  // three per sampled iteration
@@ -125,12 +125,12 @@ struct HipBackend::Impl::Batch {
             HIP_CHECK(hipMemcpyAsync(d_desc, sorted.data(), sizeof(ChainDev) * (size_t)n, hipMemcpyHostToDevice, st));
             HIP_CHECK(hipStreamSynchronize(st));
         }
-        int n_of[N_VAR] = {0, 0, 0, 0};
+        int n_of[N_VAR] = {};
         for (int i = 0; i < n; ++i) ++n_of[variant(i)];
-        for (int v = 0, first = 0; v < N_VAR; first += n_of[v], ++v) ranges[v] = Range{first, n_of[v], v >= 2, (v & 1) != 0};
+        for (int v = 0, first = 0; v < N_VAR; first += n_of[v], ++v) ranges[v] = Range{first, n_of[v], (v & 2) != 0, (v & 1) != 0, (v & 4) != 0};
 
-        size_t pair_lds[N_VAR] = {0, 0, 0, 0};
-        long long max_pairs[N_VAR] = {0, 0, 0, 0};
+        size_t pair_lds[N_VAR] = {};
+        long long max_pairs[N_VAR] = {};
         for (int i = 0; i < n; ++i) {
             const int w = variant(i);
             const size_t no = (size_t)jobs[i].n_out, cellb = geo[i].wide ? 8 : 4;
@@ -151,13 +151,14 @@ struct HipBackend::Impl::Batch {
             const dim3 colgrid((max_n_out + 3) / 4, r.count), pairgrid((unsigned)((max_pairs[w] + 3) / 4), r.count);
             with_cell(r.wide, [&](auto c) {
                 hipLaunchKernelGGL(k_init_cells<decltype(c)>, colgrid, dim3(256), 0, st, base);
-                hipLaunchKernelGGL(k_init_pairs<decltype(c)>, pairgrid, dim3(256), pair_lds[w], st, base);
+                with_flag(r.seeded, [&](auto sd) { hipLaunchKernelGGL((k_init_pairs<decltype(c), decltype(sd)::value>), pairgrid, dim3(256), pair_lds[w], st, base); });
             });
             HIP_CHECK(hipGetLastError());
         }
         for (int w = 0; w < N_VAR; ++w)
-            if (ranges[w].count) sel2_allow_lds<false>(ranges[w].wide, sel_lds[w], ranges[w].manycol);
-        for (int wide = 0; wide < 2; ++wide) upd_allow_lds(im.device, wide != 0, std::max(upd_lds[2 * wide], upd_lds[2 * wide + 1]));  // (one kernel for both carves of a width)
+            if (ranges[w].count) sel2_allow_lds<false>(ranges[w].wide, sel_lds[w], ranges[w].manycol, ranges[w].seeded);
+        for (int wide = 0; wide < 2; ++wide)  // (one limit for both carves and both tie orders of a width)
+            upd_allow_lds(im.device, wide != 0, std::max(std::max(upd_lds[2 * wide], upd_lds[2 * wide + 1]), std::max(upd_lds[4 + 2 * wide], upd_lds[4 + 2 * wide + 1])));
         HIP_CHECK(hipStreamSynchronize(st));
     }
 
@@ -200,13 +201,14 @@ struct HipBackend::Impl::Batch {
             const dim3 sel_grid((gr.count + 7) & ~7, 2);  // y = 0 search block, y = 1 substitution block
             // (+ 2: the last two blocks of a chain write the six blocks of the pairs among the modified rows)
             const dim3 upd_grid((gr.count + 7) & ~7, upd_blocks[gr.w] + 2);
-            with_sel2(ranges[gr.w].wide, ranges[gr.w].manycol, [&](auto c, auto mc) {
+            with_sel2(ranges[gr.w].wide, ranges[gr.w].manycol, ranges[gr.w].seeded, [&](auto c, auto mc, auto sd) {
                 using Cell = decltype(c);
+                constexpr bool SEEDED = decltype(sd)::value;
                 if (se) HIP_CHECK(hipEventRecord(se[0], gr.stream));
-                hipLaunchKernelGGL((k_iter_select2<Cell, false, decltype(mc)::value>), sel_grid, dim3(SEL2_THREADS), sel_lds[gr.w], gr.stream, base, gr.count, im.d_done, step);
+                hipLaunchKernelGGL((k_iter_select2<Cell, false, decltype(mc)::value, SEEDED>), sel_grid, dim3(SEL2_THREADS), sel_lds[gr.w], gr.stream, base, gr.count, im.d_done, step);
                 if (se) HIP_CHECK(hipEventRecord(se[1], gr.stream));
                 with_flag(with_stats, [&](auto s) {
-                    hipLaunchKernelGGL((k_iter_update<Cell, decltype(s)::value>), upd_grid, dim3(UPD_THREADS), upd_lds[gr.w], gr.stream, base, gr.count);
+                    hipLaunchKernelGGL((k_iter_update<Cell, decltype(s)::value, SEEDED>), upd_grid, dim3(UPD_THREADS), upd_lds[gr.w], gr.stream, base, gr.count);
                 });
                 if (se) HIP_CHECK(hipEventRecord(se[2], gr.stream));
             });

@@ -66,20 +66,21 @@ struct Geometry {
     uint32_t C, rl_cap;
 };
 
-// The unsharded instantiation of k_iter_select2 for a cell width and a carve of the substitution block: f(Cell{}, std::bool_constant<MANYCOL>{})
-template <class F> void with_sel2(bool wide, bool manycol, F &&f) {
-    with_cell(wide, [&](auto c) { with_flag(manycol, [&](auto mc) { f(c, mc); }); });
+// The unsharded instantiation of k_iter_select2 for a cell width, a carve of the substitution block and a tie order:
+// f(Cell{}, std::bool_constant<MANYCOL>{}, std::bool_constant<SEEDED>{})
+template <class F> void with_sel2(bool wide, bool manycol, bool seeded, F &&f) {
+    with_cell(wide, [&](auto c) { with_flag(manycol, [&](auto mc) { with_flag(seeded, [&](auto sd) { f(c, mc, sd); }); }); });
 }
 // raises the dynamic-LDS limit of the selection kernel the chains of that width and carve are about to be launched with (column-sharded
 // chains have the regular carve only)
-template <bool SHARDED> void sel2_allow_lds(bool wide, size_t bytes, bool manycol = false) {
+template <bool SHARDED> void sel2_allow_lds(bool wide, size_t bytes, bool manycol = false, bool seeded = false) {
     if constexpr (SHARDED)
         with_cell(wide, [&](auto c) {
             HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_select2<decltype(c), true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         });
     else
-        with_sel2(wide, manycol, [&](auto c, auto mc) {
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_select2<decltype(c), false, decltype(mc)::value>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        with_sel2(wide, manycol, seeded, [&](auto c, auto mc, auto sd) {
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_select2<decltype(c), false, decltype(mc)::value, decltype(sd)::value>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         });
 }
 
@@ -108,6 +109,7 @@ void fill_job(ChainDev &d, const ChainJob &j, int n_loc, int col0, unsigned char
     d.pn_out = j.n_out;
     d.col0 = col0;
     d.method = j.method;
+    d.tie_seed = j.tie_seed;
     d.adder_size = j.adder_size;
     d.carry_size = j.carry_size;
     d.kernel = reinterpret_cast<const float *>(io + L.kernel);
@@ -128,6 +130,7 @@ size_t sel2_fixed_lds(int n_out, const Geometry &g, bool manycol = false) {
 // What the device leaves for it: the per-workgroup LDS limit less the kernel's STATIC __shared__ arrays (the search block's bound / work lists,
 // the substitution block's partner ids: 42 768 bytes with 2048 group records -- asked from the runtime, not assumed), less a small reserve.  Static + dynamic beyond the limit
 // fails in hipFuncSetAttribute or at launch with a raw HIP error; the caller turns it into a clear message.
+// (asked of the unseeded instantiation: the static arrays of a kernel do not depend on its tie order)
 size_t sel2_lds_budget(int device, bool wide, bool manycol = false) {
     static std::mutex mu;
     static size_t cached[2][2] = {{0, 0}, {0, 0}};
@@ -135,7 +138,7 @@ size_t sel2_lds_budget(int device, bool wide, bool manycol = false) {
     if (!cached[wide][manycol]) {
         hipFuncAttributes fa;
         const void *fn = nullptr;
-        with_sel2(wide, manycol, [&](auto c, auto mc) { fn = reinterpret_cast<const void *>(&k_iter_select2<decltype(c), false, decltype(mc)::value>); });
+        with_sel2(wide, manycol, false, [&](auto c, auto mc, auto) { fn = reinterpret_cast<const void *>(&k_iter_select2<decltype(c), false, decltype(mc)::value>); });
         HIP_CHECK(hipFuncGetAttributes(&fa, fn));
         int limit = 0;
         HIP_CHECK(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
@@ -165,6 +168,8 @@ void upd_allow_lds(int device, bool wide, size_t bytes) {
     with_cell(wide, [&](auto c) {
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     });
 }
 // words of the optional LDS area in which the substitution block combines the row bitmaps of a young chain: dropped (0: every wave ORs its words

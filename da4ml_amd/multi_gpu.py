@@ -300,6 +300,43 @@ def solve_candidates_sharded(kernel, method0: str = 'wmc', method1: str = 'auto'
     return box[0]
 
 
+def solve_restarts_sharded(kernel, n_restarts: int, seed: int = 0, solver=None, **opts):
+    """``da4ml_amd.cmvm.solve_restarts`` with the restarts sharded over the ranks: restart ``r`` (tie seed
+    ``cmvm.restart_seeds(n_restarts, seed)[r]``) runs on rank ``r % world``, each rank's restarts in one call on its own GPU.
+    The shape of ``solve_candidates_sharded``: one all-reduce(MIN) over the cost vector, the first-strict-minimum rule, a
+    broadcast of the winning Pipeline from the rank that owns it.  Every rank returns the same Pipeline, identical to the
+    one-process ``solve_restarts``.  ``solver(kernels, seeds=..., **opts)`` defaults to the HIP path (``_binary.solve_many``);
+    the CPU tests inject a stand-in."""
+    import torch
+    import torch.distributed as dist
+
+    from .cmvm import first_strict_minimum, restart_seeds
+
+    rank, world, local, device = init()
+    if solver is None:
+        from . import _binary
+
+        if _binary.device_count() > 0:
+            _binary.set_device(local % _binary.device_count())
+        solver = _binary.solve_many
+    seeds = restart_seeds(n_restarts, seed)
+    mine = [r for r in range(len(seeds)) if r % world == rank]
+    per_kernel = {k: [v] * len(mine) for k, v in opts.items() if k in ('qintervals', 'latencies') and v is not None}
+    rest = {k: v for k, v in opts.items() if k not in ('qintervals', 'latencies')}
+    solved = dict(zip(mine, solver([kernel] * len(mine), seeds=[seeds[r] for r in mine], **rest, **per_kernel))) if mine else {}
+    costs = torch.full((len(seeds),), float('inf'), dtype=torch.float32, device=device)
+    for r, p in solved.items():
+        costs[r] = pipeline_cost_f32(p)
+    if world > 1:
+        dist.all_reduce(costs, op=dist.ReduceOp.MIN)
+    best = first_strict_minimum(costs.tolist())
+    if world == 1:
+        return solved[best]
+    box = [solved.get(best)]
+    dist.broadcast_object_list(box, src=best % world)
+    return box[0]
+
+
 # ------------------------------------------------------------------------------------------------ column-sharded chains
 class _DeviceView:
     """int32 view of ``count`` words of device memory owned by the HIP library, for ``torch.as_tensor`` (zero copy)."""

@@ -82,6 +82,20 @@ int da_solve_batch(int count, const float *const *kernels, const int64_t *n_in, 
                    const float *const *latencies, int adder_size, int carry_size, int search_all_decompose_dc,
                    da_result **results);
 
+/* da_solve_batch with a tie seed per problem (addition, no reference counterpart): random restarts of the greedy search.  Most
+ * greedy steps have several equally scored pairs; the reference takes the last of them in its sorted table.  A problem with
+ * seeds[i] != 0 settles such ties by another strict total order, derived from the seed, in every greedy chain it runs (both stages,
+ * every decompose_dc candidate and latency retry); scores are untouched, so the result is a greedy run of the same method.
+ * Contract: seed 0 (or seeds == NULL) gives the reference's result, bit for bit -- da_solve_batch and da_solve are this call with
+ * seeds == NULL; the same seed gives the same result on every run, in every batch composition and position; different seeds
+ * are independent runs.  Running R seeds of one matrix in one call and keeping the cheapest result never does worse than the
+ * reference when seed 0 is among them (da4ml_amd.cmvm.solve_restarts); the stage-1 distances of equal matrices are computed once
+ * per call.  Column-sharded solves (da_solve_sharded) take no seed. */
+int da_solve_batch_seeded(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const char *method0,
+                          const char *method1, int hard_dc, int decompose_dc, const float *const *qintervals,
+                          const float *const *latencies, int adder_size, int carry_size, int search_all_decompose_dc,
+                          const uint64_t *seeds /* [count], or NULL */, da_result **results);
+
 /* ---- column-sharded solve (BASELINE config C4; addition, no reference counterpart) ------------------------------------------
  * da_solve with every greedy chain sharded over the output COLUMNS of its matrix across `world` processes (one per GPU):
  * rank g holds the digits of columns [g n_out / world, (g+1) n_out / world), the pair-count table is replicated, and per
