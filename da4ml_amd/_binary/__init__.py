@@ -27,7 +27,7 @@ _i32p = np.ctypeslib.ndpointer(np.int32, flags='C_CONTIGUOUS')
 
 EXPORTS = (
     'da_last_error da_last_error_code da_version da_device_count da_set_device da_get_lsb_loc da_iceil_log2 da_cost_add da_int_arr_to_csd '
-    'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_batch_seeded da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
+    'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_batch_seeded da_solve_batch_opts da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
     'da_result_stats da_free da_timings da_engine_stats da_dais_run da_dais_last_error da_dais_run_on'
 ).split()
 
@@ -87,6 +87,8 @@ def lib():
     L.da_solve_batch.argtypes = [C.c_int, C.c_void_p, _i64p, _i64p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]  # fmt: skip
     if hasattr(L, 'da_solve_batch_seeded'):  # (as da_shard_exchanged_elements below: libraries of earlier revisions lack it; asking one for seeds raises)
         L.da_solve_batch_seeded.argtypes = L.da_solve_batch.argtypes[:-1] + [C.c_void_p, C.c_void_p]
+    if hasattr(L, 'da_solve_batch_opts'):  # (likewise)
+        L.da_solve_batch_opts.argtypes = [C.c_int, C.c_void_p, _i64p, _i64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.da_solve_sharded.restype = C.c_void_p
     L.da_solve_sharded.argtypes = [_f32p, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, _i64p]  # fmt: skip
@@ -370,6 +372,75 @@ def solve_many(
             raise RuntimeError(f'{_LIB_PATH} has no da_solve_batch_seeded: tie seeds need the library of this revision')
         rc = lib().da_solve_batch_seeded(n, kptr, n_in, n_out, method0.encode(), method1.encode(), int(hard_dc), int(decompose_dc), qptr, lptr,
                                          int(adder_size), int(carry_size), int(bool(search_all_decompose_dc)), seed_arr.ctypes.data, res)  # fmt: skip
+    if rc != 0:
+        _raise(rc)
+    return [_collect(res[i], _stats) for i in range(n)]
+
+
+DC_WEIGHT_DEFAULT = -1.0  # DA_DC_WEIGHT_DEFAULT: the reference's constant per method
+
+
+class SolveOpts(C.Structure):
+    """``da_solve_opts`` (include/da4ml_hip.h): the options of one problem of ``da_solve_batch_opts``"""
+
+    _fields_ = [
+        ('struct_size', C.c_uint32),
+        ('method0', C.c_char_p),
+        ('method1', C.c_char_p),
+        ('hard_dc', C.c_int),
+        ('decompose_dc', C.c_int),
+        ('adder_size', C.c_int),
+        ('carry_size', C.c_int),
+        ('search_all_decompose_dc', C.c_int),
+        ('dc_weight', C.c_float),
+        ('seed', C.c_uint64),
+    ]
+
+
+_EACH_DEFAULTS = dict(method0='wmc', method1='auto', hard_dc=-1, decompose_dc=-2, adder_size=-1, carry_size=-1, search_all_decompose_dc=True, seed=0, dc_weight=None)
+
+
+def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool = False):
+    """Solve independent problems concurrently, each with options of its own (``da_solve_batch_opts``, include/da4ml_hip.h).
+
+    ``options``: one dict per kernel of ``solve``'s keywords (``method0``, ``method1``, ``hard_dc``, ``decompose_dc``, ``adder_size``,
+    ``carry_size``, ``search_all_decompose_dc``) plus ``seed`` (tie seed, 0: the reference's order) and ``dc_weight`` (latency-penalty
+    weight of the ``*-dc`` / ``*-pdc`` selectors: a finite number >= 0, or ``None``: the reference's constant per method).  Missing keys
+    have ``solve``'s defaults.  ``qintervals`` / ``latencies`` as for ``solve_many``.  The result of a problem depends on nothing but its
+    own matrix and options.  ``da4ml_amd.cmvm.solve_tradeoff`` is the user-facing entry for weight sweeps."""
+    ks = [_kernel(k) for k in kernels]
+    n = len(ks)
+    if len(options) != n:
+        raise ValueError('options must hold one dict per kernel')
+    if n == 0:
+        return []
+    if not hasattr(lib(), 'da_solve_batch_opts'):
+        raise RuntimeError(f'{_LIB_PATH} has no da_solve_batch_opts: per-problem options need the library of this revision')
+    opts = (SolveOpts * n)()
+    for i, given in enumerate(options):
+        unknown = set(given) - set(_EACH_DEFAULTS)
+        if unknown:
+            raise TypeError(f'options[{i}]: unknown keys {sorted(unknown)}')
+        o = {**_EACH_DEFAULTS, **given}
+        w = DC_WEIGHT_DEFAULT if o['dc_weight'] is None else float(o['dc_weight'])
+        if o['dc_weight'] is not None and not (0.0 <= w < float('inf')):  # (a negative number is not a way to spell "unset" here)
+            raise ValueError('dc_weight must be a finite number >= 0')
+        opts[i] = SolveOpts(C.sizeof(SolveOpts), o['method0'].encode(), o['method1'].encode(), int(o['hard_dc']), int(o['decompose_dc']), int(o['adder_size']),
+                            int(o['carry_size']), int(bool(o['search_all_decompose_dc'])), w, int(o['seed']) & 0xFFFFFFFFFFFFFFFF)  # fmt: skip
+    n_in = np.array([k.shape[0] for k in ks], np.int64)
+    n_out = np.array([k.shape[1] for k in ks], np.int64)
+    kptr = (C.c_void_p * n)(*[k.ctypes.data for k in ks])
+    keep, qptr, lptr = [], None, None
+    if qintervals is not None or latencies is not None:
+        qs, ls = [], []
+        for i in range(n):
+            q, l = _opt_arrays(None if qintervals is None else qintervals[i], None if latencies is None else latencies[i], int(n_in[i]))
+            keep += [q, l]
+            qs.append(None if q is None else q.ctypes.data)
+            ls.append(None if l is None else l.ctypes.data)
+        qptr, lptr = (C.c_void_p * n)(*qs), (C.c_void_p * n)(*ls)
+    res = (C.c_void_p * n)()
+    rc = lib().da_solve_batch_opts(n, kptr, n_in, n_out, C.cast(opts, C.c_void_p), qptr, lptr, res)
     if rc != 0:
         _raise(rc)
     return [_collect(res[i], _stats) for i in range(n)]

@@ -1,11 +1,11 @@
 """Public CMVM surface -- mirrors the reference's ``da4ml.cmvm`` (src/da4ml/cmvm/__init__.py:7-29)."""
 
 from collections.abc import Callable
-from typing import TypedDict
+from typing import NamedTuple, TypedDict
 
 import numpy as np
 
-from .._binary import kernel_decompose, solve, solve_many
+from .._binary import kernel_decompose, solve, solve_each, solve_many
 from ..types import CombLogic, Op, QInterval
 
 
@@ -70,4 +70,68 @@ def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = Fa
     return (best, pipes, costs) if return_all else pipes[best]
 
 
-__all__ = ['solve', 'solve_many', 'solve_restarts', 'QInterval', 'Op', 'CombLogic', 'kernel_decompose', 'solver_options_t']
+class TradeoffPoint(NamedTuple):
+    """One solve of ``solve_tradeoff``: ``method0`` / ``method1`` / ``dc_weight`` are ``None`` where the point left them to ``solve_options``
+    (point 0) resp. to the method's own constant."""
+
+    cost: float
+    latency: float
+    method0: str | None
+    method1: str | None
+    dc_weight: float | None
+    pipeline: object
+
+
+def pareto_front(points) -> list:
+    """The points no other point beats in both cost and latency: ascending latency, strictly decreasing cost.  Of equal (cost, latency) the
+    earliest point stays."""
+    front = []
+    for _, p in sorted(enumerate(points), key=lambda ip: (ip[1].latency, ip[1].cost, ip[0])):
+        if not front or p.cost < front[-1].cost:
+            front.append(p)
+    return front
+
+
+def solve_tradeoff(kernel, weights=(0.5, 1, 2, 4, 8, 16, 32, 64), methods=('wmc-pdc', 'wmc-dc'), return_all: bool = False, **solve_options):
+    """The cost / latency trade-off of one matrix (addition to the reference API; ``solve_options``: the keywords of ``solve`` and no others --
+    ``seed`` and ``dc_weight`` are a ``TypeError``).
+
+    The ``*-dc`` / ``*-pdc`` selectors score a pair as its (weighted) count less ``w`` times the latency difference of its two rows; the
+    reference fixes ``w`` (256 for ``wmc-*``, 1e9 for ``mc-*``), which leaves three points between cheap and shallow.  Smaller weights fill
+    the gap, but not monotonically, so they are swept: point 0 is ``solve(kernel, **solve_options)`` itself, then for every method ``m`` of
+    ``methods`` the solve with ``method0 = method1 = m`` at the method's own weight and at every weight of ``weights``.  All points go to
+    the device in ONE call (``_binary.solve_each``) and run side by side; the stage-1 distances of the matrix are computed once.
+
+    Cost is the float32 cost as the reference accumulates it (``multi_gpu.pipeline_cost_f32``), latency the largest output latency of the
+    last stage.  Returns the Pareto front: a list of ``TradeoffPoint``, ascending latency, strictly decreasing cost; of equal (cost,
+    latency) the earliest point stays, so point 0 is never displaced by an equal.  ``return_all=True``: ``(front, all points)``.
+    ``cheapest_within(front, max_latency)`` picks from it."""
+    from ..multi_gpu import pipeline_cost_f32
+
+    for key in ('seed', 'dc_weight'):  # (solve takes neither: point 0 would no longer be solve(kernel, **solve_options))
+        if key in solve_options:
+            raise TypeError(f"solve_tradeoff() takes solve's keywords: {key!r} is not one of them")
+    per_kernel = {k: solve_options[k] for k in ('qintervals', 'latencies') if solve_options.get(k) is not None}
+    base = {k: v for k, v in solve_options.items() if k not in ('qintervals', 'latencies')}
+    labels = [(None, None, None)]
+    options = [dict(base)]
+    for m in methods:
+        for w in (None, *weights):
+            labels.append((m, m, None if w is None else float(w)))
+            options.append({**base, 'method0': m, 'method1': m, 'dc_weight': w})
+    n = len(options)
+    pipes = solve_each([kernel] * n, options, **{k: [v] * n for k, v in per_kernel.items()})
+    points = [TradeoffPoint(pipeline_cost_f32(p), float(max(p.out_latencies, default=0.0)), *lab, p) for lab, p in zip(labels, pipes)]
+    front = pareto_front(points)
+    return (front, points) if return_all else front
+
+
+def cheapest_within(front, max_latency: float):
+    """The member of ``front`` (``solve_tradeoff``) of least cost whose latency is at most ``max_latency``; ``ValueError`` when there is none."""
+    ok = [p for p in front if p.latency <= max_latency]
+    if not ok:
+        raise ValueError(f'no point with latency <= {max_latency}: the smallest latency available is {min(p.latency for p in front)}')
+    return min(ok, key=lambda p: p.cost)
+
+
+__all__ = ['solve', 'solve_many', 'solve_restarts', 'solve_tradeoff', 'cheapest_within', 'TradeoffPoint', 'QInterval', 'Op', 'CombLogic', 'kernel_decompose', 'solver_options_t']

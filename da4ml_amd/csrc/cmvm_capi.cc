@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <limits>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -175,33 +176,38 @@ int da_kernel_decompose(const float *kernel, int64_t n_in, int64_t n_out, int dc
     }
 }
 
-int da_solve_batch_seeded(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const char *method0,
-                          const char *method1, int hard_dc, int decompose_dc, const float *const *qintervals,
-                          const float *const *latencies, int adder_size, int carry_size, int search_all_decompose_dc,
-                          const uint64_t *seeds, da_result **results) {
+int da_solve_batch_opts(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const da_solve_opts *opts,
+                        const float *const *qintervals, const float *const *latencies, da_result **results) {
     std::lock_guard<LibraryMutex> lk(g_mutex);
     try {
+        if (count > 0 && !opts) throw std::invalid_argument("opts must hold one da_solve_opts per problem");
         std::vector<da::Problem> probs((size_t)count);
         for (int i = 0; i < count; ++i) {
             da::Problem &p = probs[i];
+            const da_solve_opts &o = opts[i];
+            if (o.struct_size != sizeof(da_solve_opts)) throw std::invalid_argument("opts[" + std::to_string(i) + "].struct_size is not sizeof(da_solve_opts)");
+            if (!o.method0 || !o.method1) throw std::invalid_argument("opts[" + std::to_string(i) + "]: method0 and method1 must be strings");
+            if (o.dc_weight != DA_DC_WEIGHT_DEFAULT && !(o.dc_weight >= 0.0f && o.dc_weight <= std::numeric_limits<float>::max()))
+                throw std::invalid_argument("dc_weight must be a finite number >= 0");
             p.kernel = kernels[i];
             p.n_in = (int)n_in[i];
             p.n_out = (int)n_out[i];
             if (p.n_in <= 0 || p.n_out <= 0) throw std::invalid_argument("kernel must be a non-empty 2-D matrix");
-            p.opt.method0 = method0;
-            p.opt.method1 = method1;
-            p.opt.hard_dc = hard_dc;
-            p.opt.decompose_dc = decompose_dc;
+            p.opt.method0 = o.method0;
+            p.opt.method1 = o.method1;
+            p.opt.hard_dc = o.hard_dc;
+            p.opt.decompose_dc = o.decompose_dc;
             const float *q = qintervals ? qintervals[i] : nullptr;
             const float *l = latencies ? latencies[i] : nullptr;
             check_dyadic_steps(q, p.n_in);
             if (q)
                 for (int r = 0; r < p.n_in; ++r) p.opt.qints.push_back(da::QInt{q[3 * r], q[3 * r + 1], q[3 * r + 2]});
             if (l) p.opt.lats.assign(l, l + p.n_in);
-            p.opt.adder_size = adder_size;
-            p.opt.carry_size = carry_size;
-            p.opt.search_all = search_all_decompose_dc != 0;
-            p.opt.seed = seeds ? seeds[i] : 0;
+            p.opt.adder_size = o.adder_size;
+            p.opt.carry_size = o.carry_size;
+            p.opt.search_all = o.search_all_decompose_dc != 0;
+            p.opt.seed = o.seed;
+            p.opt.dc_weight = o.dc_weight == DA_DC_WEIGHT_DEFAULT ? -1.0f : o.dc_weight + 0.0f;  // (+ 0: -0 and 0 are one weight)
         }
         std::vector<da::ChainStats> stats;
         const auto t0 = std::chrono::steady_clock::now();
@@ -213,6 +219,21 @@ int da_solve_batch_seeded(int count, const float *const *kernels, const int64_t 
     } catch (const std::exception &e) {
         return fail(e);
     }
+}
+
+int da_solve_batch_seeded(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const char *method0,
+                          const char *method1, int hard_dc, int decompose_dc, const float *const *qintervals,
+                          const float *const *latencies, int adder_size, int carry_size, int search_all_decompose_dc,
+                          const uint64_t *seeds, da_result **results) {
+    std::vector<da_solve_opts> opts;
+    try {  // (an allocation failure must not cross the C ABI)
+        opts.assign((size_t)std::max(count, 0), da_solve_opts{(uint32_t)sizeof(da_solve_opts), method0, method1, hard_dc, decompose_dc, adder_size, carry_size,
+                                                              search_all_decompose_dc, DA_DC_WEIGHT_DEFAULT, 0});
+        for (int i = 0; i < count; ++i) opts[i].seed = seeds ? seeds[i] : 0;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+    return da_solve_batch_opts(count, kernels, n_in, n_out, opts.data(), qintervals, latencies, results);
 }
 
 int da_solve_batch(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const char *method0,

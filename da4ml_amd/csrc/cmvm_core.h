@@ -248,7 +248,15 @@ DA_HD uint32_t float_rank(float s) {
 
 // rank of one table entry; 0 = cannot be selected.  Larger rank == larger reference score; equal rank ==
 // equal score (indexers.cc:6-90).  `ov` = n_overlap, `dl` = |lat0 - lat1|.
-DA_HD uint32_t entry_rank(uint32_t count, int ov, float dl, int method) {
+// The -dc / -pdc methods subtract a latency penalty: score = float(count) - w * dl (mc-*), float(u32 count * ov) - w * dl (wmc-*), the multiply
+// and the subtract each rounded once (never fused: the host is built with -ffp-contract=off).  The reference's w is DC_WEIGHT_MC resp.
+// DC_WEIGHT_WMC; mc, wmc and dummy read none.
+constexpr float DC_WEIGHT_MC = 1e9f, DC_WEIGHT_WMC = 256.0f;
+DA_HD float dc_weight_default(int method) { return method == M_MC_DC || method == M_MC_PDC ? DC_WEIGHT_MC : DC_WEIGHT_WMC; }
+namespace detail {
+// The one body behind both forms of entry_rank.  Two weights, one per family, because the method is a run-time value: the four-argument form
+// hands in both constants, so that each stays a literal of its own instruction, the five-argument form the chain's weight twice.
+DA_HD uint32_t entry_rank_weights(uint32_t count, int ov, float dl, int method, float w_mc, float w_wmc) {
     if (count < 2) return 0;
     switch (method) {
     case M_MC: return count + 1;
@@ -267,9 +275,9 @@ DA_HD uint32_t entry_rank(uint32_t count, int ov, float dl, int method) {
     case M_MC_DC:
     case M_MC_PDC: {
 #if defined(__HIP_DEVICE_COMPILE__)
-        float s = __fsub_rn((float)count, __fmul_rn(1e9f, dl));
+        float s = __fsub_rn((float)count, __fmul_rn(w_mc, dl));
 #else
-        float pen = 1e9f * dl;
+        float pen = w_mc * dl;
         float s = (float)count - pen;
 #endif
         if (method == M_MC_DC && !(s >= 0.0f)) return 0;
@@ -279,9 +287,9 @@ DA_HD uint32_t entry_rank(uint32_t count, int ov, float dl, int method) {
     case M_WMC_PDC: {
         uint32_t prod = count * (uint32_t)ov;  // unsigned wrap for negative overlap, as in the reference
 #if defined(__HIP_DEVICE_COMPILE__)
-        float s = __fsub_rn((float)prod, __fmul_rn(256.0f, dl));
+        float s = __fsub_rn((float)prod, __fmul_rn(w_wmc, dl));
 #else
-        float pen = 256.0f * dl;
+        float pen = w_wmc * dl;
         float s = (float)prod - pen;
 #endif
         if (method == M_WMC_DC && !(s >= 0.0f)) return 0;
@@ -290,6 +298,11 @@ DA_HD uint32_t entry_rank(uint32_t count, int ov, float dl, int method) {
     default: return 0;
     }
 }
+}  // namespace detail
+// rank with the weight `w` in place of the method's constant
+DA_HD uint32_t entry_rank(uint32_t count, int ov, float dl, int method, float w) { return detail::entry_rank_weights(count, ov, dl, method, w, w); }
+// the reference's scores: every method with its own constant
+DA_HD uint32_t entry_rank(uint32_t count, int ov, float dl, int method) { return detail::entry_rank_weights(count, ov, dl, method, DC_WEIGHT_MC, DC_WEIGHT_WMC); }
 
 // tie-break word: larger == later in the reference's sorted table (id1, id0, sub, shift)
 DA_HD uint64_t tie_word(uint32_t id0, uint32_t id1, int idx) {

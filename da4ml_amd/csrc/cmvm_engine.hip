@@ -377,6 +377,8 @@ struct ChainDev {
                                       // best entry; [2],[3] scratch; [4] sum over the steps of the longest wave's re-read rounds
     unsigned long long tie_seed;      // 0: ties are settled as the reference settles them; else the chain's seeded tie order (cmvm_core.h) -- a random restart.  Read by
                                       // the SEEDED instantiations of the kernels only (last field: the offsets the others use are what they were)
+    float dc_weight;                  // latency-penalty weight of the -dc / -pdc methods (entry_rank, cmvm_core.h); the host always fills it, by default with the method's
+                                      // constant.  Read by the WEIGHTED instantiations only: the others keep the constant as a literal (last field, as tie_seed was)
 };
 
 __constant__ Log2Table c_log2;
@@ -503,6 +505,19 @@ template <bool SEEDED> __device__ __forceinline__ uint32_t blk_pos(uint32_t k, u
         return tie_block_pos(k, seed);
     else
         return k;
+}
+
+// ---- rank of a table entry.  WEIGHTED is a template parameter of the kernels that form ranks (k_init_pairs, k_iter_update), as SEEDED is: a chain
+// whose weight is its method's constant runs the instantiations that hold the constant as a literal -- register for register what they were --,
+// a chain with another weight carries its bits (`dcw`) in a scalar register: read from the descriptor with the other fields of the step, handed to
+// the table operations as an argument (the chain context stays what it was: the selection kernel, which forms no rank, is built from it too).
+// All four sites that form a rank go through this (table_insert, table_update, and in update_partners the side-by-side re-evaluation and the
+// block creation): one site left on the constant gives valid graphs whose picks depend on where a block lies in the table.
+template <bool WEIGHTED> __device__ __forceinline__ uint32_t rank_of(const Ctx &c, uint32_t dcw, uint32_t n, int ov, float dl) {
+    if constexpr (WEIGHTED)
+        return entry_rank(n, ov, dl, c.method, u2f(dcw));
+    else
+        return entry_rank(n, ov, dl, c.method);
 }
 
 // launch_id: 2 * iteration for k_iter_select2, 2 * iteration + 1 for k_iter_update (only the low two bits are used)
@@ -636,8 +651,8 @@ __device__ __forceinline__ DA_GLOBAL uint8_t *hidx_ptr(const Ctx &c) { return re
 // ONCE PER WORKGROUP: in the first thousands of steps of a chain hundreds of blocks are created and deleted per step, and one atomic each on the
 // same line of the chain descriptor serialises in the L2 at ~12 ns apiece -- behind which every later load of the issuing wave waits (vmcnt is
 // in-order): measured in round 6, k_iter_update of steps 0 - 2000 took 24.8 us for one chain where the late steps take 6.7.
-template <bool SEEDED = false, class CntFn>
-__device__ bool table_insert(const Ctx &c, uint32_t lo, uint32_t hi, const RowInfo &ra, const RowInfo &rb, CntFn cnt_of, unsigned long long *w_out = nullptr, bool tally = true) {
+template <bool SEEDED = false, bool WEIGHTED = false, class CntFn>
+__device__ bool table_insert(const Ctx &c, uint32_t lo, uint32_t hi, const RowInfo &ra, const RowInfo &rb, CntFn cnt_of, unsigned long long *w_out = nullptr, bool tally = true, uint32_t dcw = 0) {
     int lane = lane_id();
     unsigned long long key = pack_pair(lo, hi);
     int slot = table_claim(c, key, hash_pair(lo, hi));
@@ -653,7 +668,7 @@ __device__ bool table_insert(const Ctx &c, uint32_t lo, uint32_t hi, const RowIn
         uint32_t n = k < c.K ? cnt_of(k) : 0u;
         if (n > 65535u) c.g->error = E_COUNT_OVERFLOW;
         cnt[k] = (uint16_t)n;
-        uint32_t r = entry_rank(n, ov, dl, c.method);
+        uint32_t r = rank_of<WEIGHTED>(c, dcw, n, ov, dl);
         unsigned long long cand = r ? (((unsigned long long)r << 8) | blk_pos<SEEDED>((unsigned)k, c.seed)) : 0ull;
         best = cand > best ? cand : best;
     }
@@ -700,8 +715,8 @@ __device__ __forceinline__ void block_commit(const Ctx &c, int slot, unsigned lo
 
 // Re-evaluate a block after its counts changed (new_cnt(k, old) -> new count); deletes it when no count >= 2.
 // Returns the bound word of the block's best entry afterwards (0: deleted, or nothing selectable); wave-uniform.
-template <bool SEEDED = false, class CntFn>
-__device__ unsigned long long table_update(const Ctx &c, int slot, unsigned long long key, CntFn new_cnt, bool tally = true, int *deleted = nullptr) {
+template <bool SEEDED = false, bool WEIGHTED = false, class CntFn>
+__device__ unsigned long long table_update(const Ctx &c, int slot, unsigned long long key, CntFn new_cnt, bool tally = true, int *deleted = nullptr, uint32_t dcw = 0) {
     int lane = lane_id();
     const BlkHdr h = load_hdr(c, slot);
     DA_GLOBAL uint16_t *cnt = blk_cnt(c, slot);
@@ -712,7 +727,7 @@ __device__ unsigned long long table_update(const Ctx &c, int slot, unsigned long
         uint32_t n = new_cnt(k, old);
         if (n != old) cnt[k] = (uint16_t)n;
         alive |= n >= 2;
-        uint32_t r = entry_rank(n, h.ov, h.dl, c.method);
+        uint32_t r = rank_of<WEIGHTED>(c, dcw, n, h.ov, h.dl);
         unsigned long long cand = r ? (((unsigned long long)r << 8) | blk_pos<SEEDED>((unsigned)k, c.seed)) : 0ull;
         best = cand > best ? cand : best;
     }
@@ -867,7 +882,7 @@ __device__ __forceinline__ bool wave_any_ge2(const uint32_t *cnt, int K) {
 
 // ------------------------------------------------------------------------------------------------ k_init_pairs
 // grid (ceil(n_pairs / 4), n_chains): one wave per initial row pair (i0 <= i1).
-template <class Cell, bool SEEDED = false> __global__ void __launch_bounds__(256) k_init_pairs(ChainDev *chains) {
+template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __global__ void __launch_bounds__(256) k_init_pairs(ChainDev *chains) {
     ChainDev *g = &chains[blockIdx.y];
     if (g->method == M_DUMMY) return;
     const Ctx c = make_ctx<SEEDED>(g, 0);
@@ -889,7 +904,7 @@ template <class Cell, bool SEEDED = false> __global__ void __launch_bounds__(256
         if (lane_id() == 0) g->unknown_hit = 1;
         return;
     }
-    table_insert<SEEDED>(c, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; });
+    table_insert<SEEDED, WEIGHTED>(c, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; }, nullptr, true, WEIGHTED ? f2u(g->dc_weight) : 0u);
 }
 
 // ================================================================================= k_iter_select2: the next pick, one step ahead
@@ -1926,9 +1941,10 @@ template <class Cell> struct UpdStep {
     const DA_GLOBAL uint16_t *cmap;
     const DA_GLOBAL typename RowFmt<Cell>::Entry *rl;
     const DA_GLOBAL unsigned long long *plist;
+    uint32_t dcw;  // the bits of the chain's latency-penalty weight in the WEIGHTED instantiations, unused (0) in the others
 };
 // ONE round trip: every descriptor field an update worker needs, pinned before the first branch (pin_sgpr)
-template <class Cell, bool SEEDED = false> __device__ __forceinline__ UpdStep<Cell> load_upd_step(ChainDev *gq) {
+template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __forceinline__ UpdStep<Cell> load_upd_step(ChainDev *gq) {
     using Entry = typename RowFmt<Cell>::Entry;
     UpdStep<Cell> u;
     int iter = gq->iter;
@@ -1936,6 +1952,10 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ UpdStep<Ce
     u.A = gq->A, u.B = gq->B, u.Nw = gq->Nw;
     u.shift = gq->pk_shift, u.sub = gq->pk_sub;
     u.c = make_ctx_raw<SEEDED>(gq, 2 * iter - 1);
+    if constexpr (WEIGHTED)
+        u.dcw = f2u(gq->dc_weight);
+    else
+        u.dcw = 0;
     // the step being applied is iter - 1 (the selection has counted it): its search left the best entry the step does not touch in
     // spec[(iter - 1) & 1]; the best entry of every block this launch writes that reaches it goes to c_list[(iter - 1) & 1] (fold_entry)
     u.c.rword = gq->spec[(iter - 1) & 1].word;
@@ -1950,6 +1970,7 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ UpdStep<Ce
     pin_sgpr(u.c.n_out, u.c.n_bits, u.c.K, u.c.Kpad, u.c.method, u.c.gs_log2, u.c.pb_log2, u.c.cmask, u.c.windows, u.c.hkey, u.c.hrank, u.c.hblk, u.c.grec, u.c.rows);
     pin_sgpr(u.c.rword, u.c.cn, u.c.cl);
     if constexpr (SEEDED) pin_sgpr(u.c.seed);
+    if constexpr (WEIGHTED) pin_sgpr(u.dcw);
     u.c.tomb = KEY_TOMB - (unsigned long long)((2 * iter - 1) & 3);
     ctx_finish(u.c);
     return u;
@@ -1987,13 +2008,14 @@ template <class Cell> __device__ __forceinline__ void copy_handoff(const UpdStep
 // partner, `rnew` the record of the new row.
 // STATS: tally the blocks found / created / deleted (benchmark instrumentation and the "peak pair blocks" statistic, DA4ML_HIP_STATS=1); the ballots, population
 // counts and the scalar registers of the three counters are 1.8 % of the batch's step (measured: 27.9 -> 27.5 us, one chain 19.5 -> 19.0), so the product runs without them
-template <class Cell, bool STATS, bool SEEDED = false>
+template <class Cell, bool STATS, bool SEEDED = false, bool WEIGHTED = false>
 __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell> &u, const UpdLds<Cell> &s, int first, int stride, int limit, unsigned long long ref_next,
                                                 const RowInfo &rnew, unsigned int &found, unsigned int &inserts, unsigned int &deletes) {
     using F = RowFmt<Cell>;
     using Entry = typename F::Entry;
     constexpr int HW = ((sizeof(Cell) == 4 ? 24 : 60) + HL - 1) / HL;  // count words per lane (a block's words over its HL lanes): narrow layout Kpad / 2 <= 24 words, wide <= 60
     const Ctx &c = u.c;
+    const uint32_t dcw = u.dcw;
     const uint32_t A = u.A, B = u.B, Nw = u.Nw;
     const int m = u.m, n_in = u.n_in, pk_shift = u.shift, pk_sub = u.sub;
     const DA_GLOBAL Entry *rl = u.rl;
@@ -2155,7 +2177,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const uint32_t n0 = o0 - d[2 * j], n1 = o1 - d[2 * j + 1];
                     if (n0 != o0 || n1 != o1) reinterpret_cast<DA_GLOBAL uint32_t *>(blk_ptr(c, sX) + 16)[j] = (n0 & 0xFFFFu) | (n1 << 16);
                     alive |= (n0 >= 2u) | (n1 >= 2u);
-                    const uint32_t r0 = entry_rank(n0, ov, dl, c.method), r1 = entry_rank(n1, ov, dl, c.method);
+                    const uint32_t r0 = rank_of<WEIGHTED>(c, dcw, n0, ov, dl), r1 = rank_of<WEIGHTED>(c, dcw, n1, ov, dl);
                     const unsigned long long c0 = r0 ? (((unsigned long long)r0 << 8) | blk_pos<SEEDED>((unsigned)(2 * j), c.seed)) : 0ull;
                     const unsigned long long c1 = r1 ? (((unsigned long long)r1 << 8) | blk_pos<SEEDED>((unsigned)(2 * j + 1), c.seed)) : 0ull;
                     best = c0 > best ? c0 : best;
@@ -2222,7 +2244,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const uint32_t n0 = cN[2 * j], n1 = cN[2 * j + 1];  // (zero beyond K: nothing ever counts there)
                     if ((n0 | n1) > 65535u) c.g->error = E_COUNT_OVERFLOW;
                     reinterpret_cast<DA_GLOBAL uint32_t *>(blk_ptr(c, nslot) + 16)[j] = (n0 & 0xFFFFu) | (n1 << 16);
-                    const uint32_t r0 = entry_rank(n0, ovn, dln, c.method), r1 = entry_rank(n1, ovn, dln, c.method);
+                    const uint32_t r0 = rank_of<WEIGHTED>(c, dcw, n0, ovn, dln), r1 = rank_of<WEIGHTED>(c, dcw, n1, ovn, dln);
                     const unsigned long long c0 = r0 ? (((unsigned long long)r0 << 8) | blk_pos<SEEDED>((unsigned)(2 * j), c.seed)) : 0ull;
                     const unsigned long long c1 = r1 ? (((unsigned long long)r1 << 8) | blk_pos<SEEDED>((unsigned)(2 * j + 1), c.seed)) : 0ull;
                     bestn = c0 > bestn ? c0 : bestn;
@@ -2259,7 +2281,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const int slot = table_find_from(c, pack_pair(lo, hi), hash_pair(lo, hi), 1);
                     if (slot >= 0) {
                         int gone = 0;
-                        table_update<SEEDED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdA[k]; }, false, &gone);
+                        table_update<SEEDED, WEIGHTED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdA[k]; }, false, &gone, dcw);
                         if constexpr (STATS) deletes += (unsigned)gone, ++found;
                     }
                 }
@@ -2268,12 +2290,12 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const int slot = table_find_from(c, pack_pair(lo, hi), hash_pair(lo, hi), 1);
                     if (slot >= 0) {
                         int gone = 0;
-                        table_update<SEEDED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdB[k]; }, false, &gone);
+                        table_update<SEEDED, WEIGHTED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdB[k]; }, false, &gone, dcw);
                         if constexpr (STATS) deletes += (unsigned)gone, ++found;
                     }
                 }
                 if (rnewb) {
-                    table_insert<SEEDED>(c, rpr, Nw, load_row(c.rows, rpr), rnew, [&](int k) { return rcN[k]; }, nullptr, false);
+                    table_insert<SEEDED, WEIGHTED>(c, rpr, Nw, load_row(c.rows, rpr), rnew, [&](int k) { return rcN[k]; }, nullptr, false, dcw);
                     if constexpr (STATS) ++inserts;
                 }
             }
@@ -2291,7 +2313,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
 // Two workgroups per chain share the work, one pair per wavefront and ONE turn each (find -> re-count / create: the longest dependent chain
 // of this kernel; with all six in one workgroup of four waves it took two turns): part 0 the four pairs with A, part 1 (B,N), (N,N) and the
 // listed entries.
-template <class Cell, bool SEEDED = false> __device__ __forceinline__ void special_pairs(ChainDev *gq, const UpdStep<Cell> &u, int part) {
+template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __forceinline__ void special_pairs(ChainDev *gq, const UpdStep<Cell> &u, int part) {
     const Ctx &c = u.c;
     const uint32_t A = u.A, B = u.B, Nw = u.Nw;
     const bool same = A == B;
@@ -2316,13 +2338,13 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ void speci
         const int slot = existed ? table_find(c, key, hash_pair(lo, hi)) : -1;
         unsigned long long w = 0;
         if (slot >= 0)
-            w = table_update<SEEDED>(c, slot, key, [&](int k, uint32_t) { return cnt[k]; });
+            w = table_update<SEEDED, WEIGHTED>(c, slot, key, [&](int k, uint32_t) { return cnt[k]; }, true, nullptr, u.dcw);
         else {
             int f = 0;
             for (int k = lane; k < c.K; k += WAVE) f |= cnt[k] >= 2u;
             if (__any(f)) {
                 const RowInfo xa = pick_row(lo == Nw, rn, pick_row(lo == A, ra, rb)), xb = pick_row(hi == Nw, rn, pick_row(hi == A, ra, rb));
-                table_insert<SEEDED>(c, lo, hi, xa, xb, [&](int k) { return cnt[k]; }, &w);
+                table_insert<SEEDED, WEIGHTED>(c, lo, hi, xa, xb, [&](int k) { return cnt[k]; }, &w, true, u.dcw);
             }
         }
         (void)w;  // (both paths have passed the block's best entry to fold_entry)
@@ -2349,17 +2371,17 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ void speci
 
 // update_body: the partner rows [block_y * NWV * QN + ..., stride grid_y * NWV * QN) of chain `gq`'s current step, by a
 // workgroup of NWV wavefronts (k_iter_update: 256-thread blocks, grid = chains x blocks per chain).
-template <class Cell, int NWV, bool STATS, bool SEEDED = false>
+template <class Cell, int NWV, bool STATS, bool SEEDED = false, bool WEIGHTED = false>
 __device__ __forceinline__ void update_body(ChainDev *gq, bool in_range, int block_y, int grid_y) {
     constexpr int NTHR = NWV * WAVE;
     // Grid (chains padded to a multiple of 8, blocks per chain): the chain index is the FAST grid dimension.  Workgroups go to
     // the XCDs round-robin by their linear id, so all blocks of chain c -- and block c of k_iter_select, which has the same
     // linear id modulo 8 -- run on XCD c mod 8: the table lines, bounds and lists of a chain stay in ONE of the eight
     // non-coherent L2s instead of being spread over all of them.
-    const UpdStep<Cell> u = load_upd_step<Cell, SEEDED>(gq);
+    const UpdStep<Cell> u = load_upd_step<Cell, SEEDED, WEIGHTED>(gq);
     if (!in_range || u.done) return;
     if (block_y >= grid_y - 2) {  // the last two blocks of a chain: the six blocks of the pairs among {A, B, new row}
-        special_pairs<Cell, SEEDED>(gq, u, block_y - (grid_y - 2));
+        special_pairs<Cell, SEEDED, WEIGHTED>(gq, u, block_y - (grid_y - 2));
         return;
     }
     grid_y -= 2;
@@ -2381,7 +2403,7 @@ __device__ __forceinline__ void update_body(ChainDev *gq, bool in_range, int blo
     copy_handoff<Cell>(u, s, tid, NTHR);  // one pass, one barrier (the column map arrives ready-made)
     __syncthreads();
     unsigned int found = 0, inserts = 0, deletes = 0;
-    update_partners<Cell, STATS, SEEDED>(gq, u, s, gw * QN, total_waves * QN, u.n_partners, ref0, rnew, found, inserts, deletes);
+    update_partners<Cell, STATS, SEEDED, WEIGHTED>(gq, u, s, gw * QN, total_waves * QN, u.n_partners, ref0, rnew, found, inserts, deletes);
     if constexpr (!STATS) return;
     // statistics: summed per block in LDS, then ONE pair of device atomics per block.  (Four atomics per wave on one line
     // of the chain descriptor -- 640 per chain and launch, from all XCDs -- serialise at ~12 ns each and every launch had
@@ -2398,7 +2420,7 @@ __device__ __forceinline__ void update_body(ChainDev *gq, bool in_range, int blo
         if (s_stat[1] != s_stat[2]) atomicAdd(&gq->n_live, s_stat[1] - s_stat[2]);  // blocks created less blocks deleted by this workgroup (modulo 2^32)
     }
 }
-template <class Cell, bool STATS, bool SEEDED = false>
+template <class Cell, bool STATS, bool SEEDED = false, bool WEIGHTED = false>
 __global__ void __launch_bounds__(UPD_THREADS, DA_UPD_OCC) __attribute__((amdgpu_num_sgpr(DA_UPD_SGPRS))) k_iter_update(ChainDev *chains, int n_chains) {
     // Grid (chains padded to a multiple of 8, blocks per chain): the chain index is the FAST grid dimension (see update_body)
 #ifdef DA_STEP_CLOCKS
@@ -2407,7 +2429,7 @@ __global__ void __launch_bounds__(UPD_THREADS, DA_UPD_OCC) __attribute__((amdgpu
     const int clk_par = (gk->iter - 1) & 1;
     if (clk_on && threadIdx.x == 0) CLK_MARK(gk, clk_par, 2, true);
 #endif
-    update_body<Cell, UPD_WAVES, STATS, SEEDED>(&chains[(int)blockIdx.x < n_chains ? blockIdx.x : 0], (int)blockIdx.x < n_chains, (int)blockIdx.y, (int)gridDim.y);  // clamped: the descriptor read is unconditional
+    update_body<Cell, UPD_WAVES, STATS, SEEDED, WEIGHTED>(&chains[(int)blockIdx.x < n_chains ? blockIdx.x : 0], (int)blockIdx.x < n_chains, (int)blockIdx.y, (int)gridDim.y);  // clamped: the descriptor read is unconditional
 #ifdef DA_STEP_CLOCKS
     __syncthreads();
     if (clk_on && threadIdx.x == 0) CLK_MARK(gk, clk_par, 3, false);

@@ -28,16 +28,17 @@ struct HipBackend::Impl::Batch {
     std::vector<Geometry> geo;
     std::vector<size_t> a_off;  // of every chain in the arena
     size_t arena_bytes = 0, budget = 0, free_b = 0;
-    std::vector<int> order;  // descriptor s of the device is chain order[s] of the call: chains of the reference's tie order first, of those the narrow ones first, and of a width those of the regular selection carve first
+    std::vector<int> order;  // descriptor s of the device is chain order[s] of the call: chains with their method's own penalty weight first, of those the chains of the reference's tie order first, of those the narrow ones first, and of a width those of the regular selection carve first
     std::vector<char> manycol;  // per chain: it runs the many-column instantiation of k_iter_select2 (sel2_manycol)
-    static constexpr int N_VAR = 8;  // kernel variants of a batch: 4 * seeded + 2 * wide + manycol (a batch of restarts mixes tie orders: restart 0 has the reference's)
-    int variant(int i) const { return 4 * (int)(jobs[i].tie_seed != 0) + 2 * (int)geo[i].wide + (int)manycol[i]; }
+    static constexpr int N_VAR = 16;  // kernel variants of a batch: 8 * weighted + 4 * seeded + 2 * wide + manycol (a batch of restarts mixes tie orders: restart 0 has the reference's;
+                                      // a sweep of penalty weights mixes weighted chains with those on their method's constant.  The selection kernel forms no rank: it has no weighted form)
+    int variant(int i) const { return 8 * (int)chain_weighted(jobs[i]) + 4 * (int)(jobs[i].tie_seed != 0) + 2 * (int)geo[i].wide + (int)manycol[i]; }
     struct Range {
         int first, count;
-        bool wide, manycol, seeded;
+        bool wide, manycol, seeded, weighted;
     } ranges[N_VAR];
     size_t sel_lds[N_VAR] = {}, upd_lds[N_VAR] = {};  // per variant: dynamic LDS of the loop's kernels, k_iter_update blocks per chain
-    int upd_blocks[N_VAR] = {1, 1, 1, 1, 1, 1, 1, 1};
+    int upd_blocks[N_VAR] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
     EventGuard events;  // declared before anything greedy_loop declares: destroyed after its streams have been drained, and after extract has read the clocks
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> sample_ev;  // three per sampled iteration
@@ -127,7 +128,7 @@ struct HipBackend::Impl::Batch {
         }
         int n_of[N_VAR] = {};
         for (int i = 0; i < n; ++i) ++n_of[variant(i)];
-        for (int v = 0, first = 0; v < N_VAR; first += n_of[v], ++v) ranges[v] = Range{first, n_of[v], (v & 2) != 0, (v & 1) != 0, (v & 4) != 0};
+        for (int v = 0, first = 0; v < N_VAR; first += n_of[v], ++v) ranges[v] = Range{first, n_of[v], (v & 2) != 0, (v & 1) != 0, (v & 4) != 0, (v & 8) != 0};
 
         size_t pair_lds[N_VAR] = {};
         long long max_pairs[N_VAR] = {};
@@ -151,14 +152,22 @@ struct HipBackend::Impl::Batch {
             const dim3 colgrid((max_n_out + 3) / 4, r.count), pairgrid((unsigned)((max_pairs[w] + 3) / 4), r.count);
             with_cell(r.wide, [&](auto c) {
                 hipLaunchKernelGGL(k_init_cells<decltype(c)>, colgrid, dim3(256), 0, st, base);
-                with_flag(r.seeded, [&](auto sd) { hipLaunchKernelGGL((k_init_pairs<decltype(c), decltype(sd)::value>), pairgrid, dim3(256), pair_lds[w], st, base); });
+                with_flag(r.seeded, [&](auto sd) {
+                    with_flag(r.weighted, [&](auto wt) { hipLaunchKernelGGL((k_init_pairs<decltype(c), decltype(sd)::value, decltype(wt)::value>), pairgrid, dim3(256), pair_lds[w], st, base); });
+                });
             });
             HIP_CHECK(hipGetLastError());
         }
-        for (int w = 0; w < N_VAR; ++w)
-            if (ranges[w].count) sel2_allow_lds<false>(ranges[w].wide, sel_lds[w], ranges[w].manycol, ranges[w].seeded);
-        for (int wide = 0; wide < 2; ++wide)  // (one limit for both carves and both tie orders of a width)
-            upd_allow_lds(im.device, wide != 0, std::max(std::max(upd_lds[2 * wide], upd_lds[2 * wide + 1]), std::max(upd_lds[4 + 2 * wide], upd_lds[4 + 2 * wide + 1])));
+        // one limit per instantiation of the selection kernel: it has no weighted form, so the ranges w and w + 8 launch the same function and the
+        // limit must cover the larger of the two (set once per range, the second would lower what the first had just been given)
+        for (int w = 0; w < N_VAR / 2; ++w)
+            if (ranges[w].count || ranges[w + 8].count) sel2_allow_lds<false>(ranges[w].wide, std::max(sel_lds[w], sel_lds[w + 8]), ranges[w].manycol, ranges[w].seeded);
+        for (int wide = 0; wide < 2; ++wide) {  // (one limit for all instantiations of a width)
+            size_t most = 0;
+            for (int w = 0; w < N_VAR; ++w)
+                if (((w & 2) != 0) == (wide != 0)) most = std::max(most, upd_lds[w]);
+            upd_allow_lds(im.device, wide != 0, most);
+        }
         HIP_CHECK(hipStreamSynchronize(st));
     }
 
@@ -182,7 +191,7 @@ struct HipBackend::Impl::Batch {
             const Range &r = ranges[w];
             if (r.count == 0) continue;
             int parts = std::max(1, std::min(im.n_lanes, r.count / 8));
-            if (n_ranges > 1) parts = std::max(1, parts / n_ranges);  // (at most MAX_LANES groups in all)
+            if (n_ranges > 1) parts = std::max(1, parts / n_ranges);  // (groups beyond MAX_LANES share streams)
             for (int p = 0; p < parts; ++p) {
                 int lo = r.first + (int)((long long)r.count * p / parts), hi = r.first + (int)((long long)r.count * (p + 1) / parts);
                 groups.push_back(Group{lo, hi - lo, w, im.lanes[groups.size() % Impl::MAX_LANES]});
@@ -208,7 +217,9 @@ struct HipBackend::Impl::Batch {
                 hipLaunchKernelGGL((k_iter_select2<Cell, false, decltype(mc)::value, SEEDED>), sel_grid, dim3(SEL2_THREADS), sel_lds[gr.w], gr.stream, base, gr.count, im.d_done, step);
                 if (se) HIP_CHECK(hipEventRecord(se[1], gr.stream));
                 with_flag(with_stats, [&](auto s) {
-                    hipLaunchKernelGGL((k_iter_update<Cell, decltype(s)::value, SEEDED>), upd_grid, dim3(UPD_THREADS), upd_lds[gr.w], gr.stream, base, gr.count);
+                    with_flag(ranges[gr.w].weighted, [&](auto wt) {
+                        hipLaunchKernelGGL((k_iter_update<Cell, decltype(s)::value, SEEDED, decltype(wt)::value>), upd_grid, dim3(UPD_THREADS), upd_lds[gr.w], gr.stream, base, gr.count);
+                    });
                 });
                 if (se) HIP_CHECK(hipEventRecord(se[2], gr.stream));
             });
@@ -226,9 +237,11 @@ struct HipBackend::Impl::Batch {
         // The done counter is read back ONE WINDOW BEHIND on a separate stream: after window w is queued, the poll stream
         // waits for every group's end-of-window event and copies the counter; the host looks at the copy of window w-1 only
         // after window w has been queued, so the queues never drain while the host decides whether to go on.
-        hipEvent_t win_ev[2][Impl::MAX_LANES], copy_ev[2];
+        std::vector<hipEvent_t> win_ev[2];  // (one per group: a batch can hold more kernel variants than there are streams)
+        hipEvent_t copy_ev[2];
         for (int p = 0; p < 2; ++p) {
             copy_ev[p] = events.make(hipEventDisableTiming);
+            win_ev[p].resize(groups.size());
             for (size_t gi = 0; gi < groups.size(); ++gi) win_ev[p][gi] = events.make(hipEventDisableTiming);
         }
         im.h_done[0] = im.h_done[1] = 0;
@@ -255,6 +268,7 @@ struct HipBackend::Impl::Batch {
             std::thread th;
         } helper;
         const bool two_threads = im.launch_threads >= 2 && groups.size() >= 2;
+        static_assert(Impl::MAX_LANES % 2 == 0, "groups gi and gi + MAX_LANES share a stream: they must be queued by the same launching thread (gi & 1)");
         auto mine = [&](size_t gi, int who) { return !two_threads || (int)(gi & 1) == who; };
         auto window_launches = [&](int who, long long first_step, int iters, int parity, hipEvent_t *se0) {
             for (int it = 0; it < iters; ++it)

@@ -101,6 +101,15 @@ InputLayout input_layout(int n_in, int n_out, bool lats = true) {
     return L;
 }
 
+// The latency-penalty weight a chain's -dc / -pdc method scores with: the job's, or the method's constant when the job sets none (always filled in;
+// mc, wmc and dummy never read it).  A chain is WEIGHTED -- it runs the instantiations of k_init_pairs and k_iter_update that read the weight from
+// the descriptor -- when that is not, bit for bit, the constant its method has as a literal in the other instantiations.
+float chain_dc_weight(const ChainJob &j) { return j.dc_weight >= 0.0f ? j.dc_weight : dc_weight_default(j.method); }
+bool chain_weighted(const ChainJob &j) {
+    const bool dc = j.method == M_MC_DC || j.method == M_MC_PDC || j.method == M_WMC_DC || j.method == M_WMC_PDC;
+    return dc && f2u(chain_dc_weight(j)) != f2u(dc_weight_default(j.method));
+}
+
 // The job fields of a descriptor, all else zero: the chain holds the `n_loc` columns from `col0` on of the job's matrix, whose inputs are at `io`
 void fill_job(ChainDev &d, const ChainJob &j, int n_loc, int col0, unsigned char *io, const InputLayout &L) {
     std::memset(&d, 0, sizeof d);
@@ -110,6 +119,7 @@ void fill_job(ChainDev &d, const ChainJob &j, int n_loc, int col0, unsigned char
     d.col0 = col0;
     d.method = j.method;
     d.tie_seed = j.tie_seed;
+    d.dc_weight = chain_dc_weight(j);
     d.adder_size = j.adder_size;
     d.carry_size = j.carry_size;
     d.kernel = reinterpret_cast<const float *>(io + L.kernel);
@@ -170,6 +180,10 @@ void upd_allow_lds(int device, bool wide, size_t bytes) {
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     });
 }
 // words of the optional LDS area in which the substitution block combines the row bitmaps of a young chain: dropped (0: every wave ORs its words

@@ -96,6 +96,29 @@ int da_solve_batch_seeded(int count, const float *const *kernels, const int64_t 
                           const float *const *latencies, int adder_size, int carry_size, int search_all_decompose_dc,
                           const uint64_t *seeds /* [count], or NULL */, da_result **results);
 
+/* da_solve_batch with the options of every problem in a struct of its own (addition, no reference counterpart): one call can mix methods,
+ * latency budgets, tie seeds and penalty weights -- a sweep of the cost / latency trade-off of one matrix is one batch of chains.
+ * dc_weight: the selectors mc-dc, mc-pdc, wmc-dc and wmc-pdc score a pair as float(count) - w |dlat| (mc-*) resp.
+ * float(uint32 count * overlap) - w |dlat| (wmc-*), float32, the multiply and the subtract each rounded once; the reference's w is
+ * 1e9 resp. 256.  A problem with dc_weight = w (finite, >= 0) uses w in every greedy chain whose resolved method is one of the four:
+ * both stages, every decompose_dc candidate, every latency retry and the wmc-dc that hard_dc forces; mc, wmc and dummy ignore it.
+ * Contract: DA_DC_WEIGHT_DEFAULT (or the constant of the method itself) gives the reference's result, bit for bit; any other negative
+ * value, NaN or infinity gives DA_ERR_VALUE ("dc_weight must be a finite number >= 0"); the result of a problem depends on nothing but
+ * its own matrix and options, whatever else the batch holds and wherever it stands in it.  da_solve_batch_seeded, da_solve_batch and
+ * da_solve are this call with equal structs.  Small weights trade latency for adders between wmc and wmc-dc;
+ * da4ml_amd.cmvm.solve_tradeoff sweeps them in one call and returns the Pareto front.  Column-sharded solves keep the constants.
+ * struct_size must be sizeof(da_solve_opts). */
+#define DA_DC_WEIGHT_DEFAULT (-1.0f)
+typedef struct da_solve_opts {
+    uint32_t struct_size;
+    const char *method0, *method1;
+    int hard_dc, decompose_dc, adder_size, carry_size, search_all_decompose_dc;
+    float dc_weight;
+    uint64_t seed;
+} da_solve_opts;
+int da_solve_batch_opts(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const da_solve_opts *opts /* [count] */,
+                        const float *const *qintervals, const float *const *latencies, da_result **results);
+
 /* ---- column-sharded solve (BASELINE config C4; addition, no reference counterpart) ------------------------------------------
  * da_solve with every greedy chain sharded over the output COLUMNS of its matrix across `world` processes (one per GPU):
  * rank g holds the digits of columns [g n_out / world, (g+1) n_out / world), the pair-count table is replicated, and per
