@@ -1886,7 +1886,8 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false, bool SEEDED = 
 }
 
 #ifndef DA_UPD_OCC
-#define DA_UPD_OCC 5  // blocks of 256 threads per CU the register budget is capped for (88 VGPRs, no spills)
+#define DA_UPD_OCC 5  // blocks of 256 threads per CU the register budget is capped for.  The cap no longer binds: the narrow instantiations take 63 - 67 VGPRs, the wide
+                      // ones 67 - 71, none spills, at 5 and at 6 alike (80 = 512 / 6 at the granule of 8) -- up to seven waves per SIMD are resident
 #endif
 #if DA_UPD_OCC >= 8
 #define DA_UPD_SGPRS 80  // 800 SGPRs per SIMD: more than 80 per wave would cap the residency below 8 waves per SIMD
@@ -1977,14 +1978,16 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __f
 }
 // LDS of an update worker: the hand-off of the selection (consumed digits of A and B [n_out each], the substituted columns
 // [n_out], column -> 1 + index of the substituted column [n_out]) -- shared by the waves that copied it together -- and ONE
-// wave's per-partner counters [QN][3][Kpad] + a spare vector [Kpad] (counts of blocks that do not exist)
+// wave's per-partner counters [QN][Kpad] at the head of its region (the digit pairs gained with the new row; the losses of A's and B's blocks are read from them, upd_loss)
 template <class Cell> struct UpdLds {
     Cell *mA, *mB;
     int *col;
     uint16_t *cmap;
     uint32_t *cnt;
     static __device__ __forceinline__ size_t table_bytes(int n_out) { return (size_t)n_out * (2 * sizeof(Cell) + 4 + 2); }
-    static __device__ __forceinline__ size_t wave_bytes(int Kpad) { return (size_t)(QN * 3 + 1) * Kpad * 4; }  // (+ one spare vector)
+    // (a wave's region keeps the size it had with three vectors per partner and a spare one: the LDS budget check of the host and the size it reports are
+    // unchanged; only the first QN vectors are used.  LDS does not bound the residency: seven blocks of the C3 line take 7 x 10 KB of the CU's 160 KB)
+    static __device__ __forceinline__ size_t wave_bytes(int Kpad) { return (size_t)(QN * 3 + 1) * Kpad * 4; }
     __device__ __forceinline__ void carve(unsigned char *tables, unsigned char *counters, int n_out) {
         mA = reinterpret_cast<Cell *>(tables);
         mB = mA + n_out;
@@ -2001,6 +2004,17 @@ template <class Cell> __device__ __forceinline__ void copy_handoff(const UpdStep
         s.col[j] = u.mcol[j];
         s.mA[j] = u.mA[j];
     }
+}
+
+// The counts a block of a partner row loses are a RE-INDEXING of the counts the new row gains (cN, key (d, sg) at index sg W + d + nb - 1,
+// W = 2 nb - 1): the walk of update_partners counts every digit pair once, under the new row's key, and the losses are read through the
+// inverse map.  Key (d', s') of the block (X, partner) has lost cN[(s' ^ sub) W + sgn d' + cst]; a pre-image outside the W shifts reads 0.
+//   * A-role digits (in A's block):  sgn = -1 when the partner lies above A (the key is mirrored), cst = nb - 1, sub = 0;
+//   * B-role digits (in B's block, or A's when the pick is a row with itself): they sit `shift` further and their sign is flipped when
+//     the pick subtracts -- sgn = -1 when the partner lies above B, cst = nb - 1 - shift, sub = pk_sub.
+__device__ __forceinline__ uint32_t upd_loss(const uint32_t *cN, int k, int K, int W, int nbm1, int sgn, int cst, int sub) {
+    const int sg = k >= W, t = __mul24(k - (sg ? W : 0) - nbm1, sgn) + cst;
+    return (k < K && (unsigned)t < (unsigned)W) ? cN[((sg ^ sub) ? W : 0) + t] : 0u;
 }
 
 // update_partners: ONE WAVEFRONT works through the partner rows first + q, first + stride + q, ... < limit of the step (q = its
@@ -2026,9 +2040,16 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
     uint32_t *s_cnt = s.cnt;
     const int nb = c.n_bits, Kpad = c.Kpad, K = c.K;
     const int lane = lane_id();
-    const int q = lane >> QG_LOG2, l = lane & (QG - 1), qsh = q * QG;
+    // What a lane derives from its index -- group, place in the group, counter and count-word addresses, a dozen values -- is formed AGAIN in
+    // every phase of a pass from a copy of the index the optimiser cannot see through: left alone it computes them once in front of the pass loop
+    // and carries them through every pass in registers of their own, which is what kept the kernel above 80 VGPRs (six waves per SIMD).
+    auto lane_now = [&]() {
+        int v = lane;
+        pin_vgpr(v);
+        return v;
+    };
     const bool same = A == B;
-    uint32_t *dA = s_cnt + (size_t)q * 3 * Kpad, *dB = dA + Kpad, *cN = dB + Kpad;  // this group's counters
+    const int W = 2 * nb - 1;  // key indices per sign
     const int KW = Kpad / 2;  // 32-bit words of counts per block (two u16 counts each)
     UPD_TIMER_DECL
     // partner p of the list: pass p / (QN total_waves), wave (p / QN) mod total_waves, group p mod QN -- all groups of all
@@ -2038,6 +2059,8 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
 #endif
     constexpr int CH = DA_UPD_CH;  // list chunks (16 entries each) fetched together; longer lists continue in the loop below
     for (int base = first; base < limit; base += stride) {
+        const int ln = lane_now(), q = ln >> QG_LOG2, l = ln & (QG - 1), qsh = q * QG;
+        uint32_t *const cN = s_cnt + (size_t)q * Kpad;  // this group's counters
         const int idx = base + q;
         const bool valid = idx < limit;
         // ---- round trip 1: the group's partner reference (the next pass's one is fetched now: off the critical path there)
@@ -2062,7 +2085,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
             const int j = l + u * QG;
             e[u] = j < cnt ? rl[(size_t)off + (dense ? s_col[j] : j)] : F::none();
         }
-        for (int k = l; k < 3 * Kpad; k += QG) dA[k] = 0;  // while the loads are in flight
+        for (int k = l; k < Kpad; k += QG) cN[k] = 0;  // while the loads are in flight
         // ---- resolve the probes (per group: 16 bits of the wave ballots)
         int sA = SLOT_NONE, sB = SLOT_NONE;
         {
@@ -2096,7 +2119,6 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
         // and every HL-th count word
         const int half = l / HL, hl = l % HL;
         const int sX = half ? sB : sA;
-        const unsigned long long keyX = half ? keyB : keyA;
         const da_i4 z4 = da_i4{0, 0, 0, 0};
         const da_i4 hdX = sX >= 0 ? *reinterpret_cast<const DA_GLOBAL da_i4 *>(blk_ptr(c, sX)) : z4;
         uint32_t wX[HW];
@@ -2107,24 +2129,16 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
         }
         lds_fence();  // counters are zero
         // ---- digit pairs lost with A's / B's consumed digits and gained with the new row: a lane per list entry.
-        // The digit pairs (partner digit, consumed A-role digit) are walked ONCE for all the blocks they count in (round 6; three walks,
-        // one per block, were most of this phase's instructions):
-        //   * gained with the new row, whose cell in this column IS ma (the partner is the row with the smaller id): key (q - p, signs);
+        // The digit pairs (partner digit, consumed A-role digit) are walked ONCE and counted ONCE, under the key they gain with the new row,
+        // whose cell in this column IS ma (the partner is the row with the smaller id): key (q - p, signs).  What A's and B's blocks lose with
+        // the same pairs is that vector re-indexed (upd_loss):
         //   * lost with A: the same key when the partner is also below A, the mirrored one (shift negated) otherwise;
         //   * lost with the B-role digit that went with the A-role one: it sits `shift` positions further, its sign flipped when the pick
         //     subtracts (substitute_column, cmvm_core.h: mb = ma moved by shift, also when A and B are one row) -- in B's block, or in A's
         //     when the pick is a row with itself.
-        // The body of the walk is straight-line (21 instructions per digit pair, 35 with a branch per block): what depends on the partner
-        // only -- which blocks exist, which are mirrored, where the B-role key sits -- is folded into three counter addresses and two signs in
-        // front of it (a block that does not exist counts into a spare vector of the wavefront that nobody reads), the consumed digits (one
-        // per column, hardly ever more) are the OUTER loop.  Batch 29.6 -> 29.25 us per step, one chain 19.8 -> 19.65 (MI355X).
-        const bool hasA = sA != SLOT_NONE, hasB = same ? hasA : sB != SLOT_NONE;
-        const bool mirA = A < pr, mirB = same ? mirA : B < pr;
-        const int Wk4 = 4 * (2 * nb - 1), sgnA4 = mirA ? -4 : 4, sgnB4 = mirB ? -4 : 4, tau = pk_sub ? -1 : 1;  // (byte offsets into the counters)
-        unsigned char *const spare = reinterpret_cast<unsigned char *>(s_cnt + (size_t)QN * 3 * Kpad);
+        // The body of the walk is straight-line, the consumed digits (one per column, hardly ever more) are the OUTER loop.
+        const int Wk4 = 4 * W;  // (byte offsets into the counters)
         unsigned char *const pN = reinterpret_cast<unsigned char *>(cN + (nb - 1));
-        unsigned char *const pA = (hasA ? reinterpret_cast<unsigned char *>(dA) : spare) + 4 * (nb - 1);
-        unsigned char *const pB = (hasB ? reinterpret_cast<unsigned char *>(same ? dA : dB) : spare) + 4 * (nb - 1) + (pk_sub ? Wk4 : 0) + sgnB4 * pk_shift;
         auto bump = [](unsigned char *at) { atomicAdd(reinterpret_cast<uint32_t *>(at), 1u); };
         auto pairs_of = [&](const Entry en) {
             using O = CellOps<Cell>;
@@ -2146,8 +2160,6 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     pin_vgpr(sgm);  // (kept as a mask: the compiler otherwise turns the AND below into compare + move + select)
                     const int d = q_ - p_, off = sgm & Wk4;  // key (d, sg) -> index sg (2 nb - 1) + d + nb - 1
                     bump(pN + off + 4 * d);
-                    bump(pA + off + __mul24(d, sgnA4));
-                    bump(pB + __mul24(off, tau) + __mul24(d, sgnB4));
                 }
             }
         };
@@ -2163,10 +2175,20 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
         UPD_TIMER_MARK(2)  // pair enumeration
         // ---- re-evaluate both blocks at once: two counts per lane and word, reduction inside the eight lanes of a block, their last lane publishes
         {
+            const int ln = lane_now(), q = ln >> QG_LOG2, l = ln & (QG - 1), qsh = q * QG, half = l / HL, hl = l % HL;
+            const uint32_t *const cN = s_cnt + (size_t)q * Kpad;
             const bool has = sX >= 0;
             const int ov = hdX.x;
             const float dl = __int_as_float(hdX.y);
-            const uint32_t *d = half ? dB : dA;
+            // this lane's block loses the A-role pairs (lower half: A's block) or the B-role ones (upper half: B's block) -- and both when
+            // the pick is a row with itself (A's block; the upper half then has no block)
+            const uint32_t rowX = half ? B : A;
+            const int sgnX = rowX < pr ? -1 : 1, cstX = half ? nb - 1 - pk_shift : nb - 1, subX = half ? pk_sub : 0;
+            auto lost = [&](int k) {
+                uint32_t v = upd_loss(cN, k, K, W, nb - 1, sgnX, cstX, subX);
+                if (same) v += upd_loss(cN, k, K, W, nb - 1, sgnX, nb - 1 - pk_shift, pk_sub);
+                return v;
+            };
             unsigned long long best = 0;
             int alive = 0;
 #pragma unroll
@@ -2174,7 +2196,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                 const int j = hl + u * HL;
                 if (has && j < KW) {
                     const uint32_t o0 = wX[u] & 0xFFFFu, o1 = wX[u] >> 16;
-                    const uint32_t n0 = o0 - d[2 * j], n1 = o1 - d[2 * j + 1];
+                    const uint32_t n0 = o0 - lost(2 * j), n1 = o1 - lost(2 * j + 1);
                     if (n0 != o0 || n1 != o1) reinterpret_cast<DA_GLOBAL uint32_t *>(blk_ptr(c, sX) + 16)[j] = (n0 & 0xFFFFu) | (n1 << 16);
                     alive |= (n0 >= 2u) | (n1 >= 2u);
                     const uint32_t r0 = rank_of<WEIGHTED>(c, dcw, n0, ov, dl), r1 = rank_of<WEIGHTED>(c, dcw, n1, ov, dl);
@@ -2186,7 +2208,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
             }
             best = part_row_max_u64<HL>(best);  // all lanes take part (the DPP source lanes must be active); every lane of a block's HL holds its result
             const bool any_alive = (((uint32_t)(__ballot(alive != 0) >> (qsh + HL * half)) & HMASK) != 0);
-            if (has && hl == HL - 1) block_commit<SEEDED>(c, sX, keyX, BlkHdr{ov, dl, (uint32_t)hdX.z, (uint32_t)hdX.w}, best, any_alive, false);
+            if (has && hl == HL - 1) block_commit<SEEDED>(c, sX, pack_pair(min(rowX, pr), max(rowX, pr)), BlkHdr{ov, dl, (uint32_t)hdX.z, (uint32_t)hdX.w}, best, any_alive, false);
             if constexpr (STATS) deletes += (unsigned)__popcll(__ballot(has && hl == HL - 1 && !any_alive));  // (wave-uniform: the blocks this pass deleted, tallied once per workgroup)
         }
         UPD_TIMER_MARK(3)  // block updates
@@ -2198,6 +2220,8 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
         // A group whose first bucket has no free slot takes the wave-wide path below.
         bool gslow = false;  // this group's creation is left to table_insert
         if (__ballot(gnew)) {
+            const int ln = lane_now(), q = ln >> QG_LOG2, l = ln & (QG - 1), qsh = q * QG;
+            const uint32_t *const cN = s_cnt + (size_t)q * Kpad;
             const unsigned long long keyN = pack_pair(pr, Nw);  // (the partner is older than the new row)
             const uint32_t baseN = (hash_pair(pr, Nw) & ~(BUCKET - 1)) & c.cmask;
             unsigned long long kN[SPL];
@@ -2275,13 +2299,16 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                 const uint32_t rpr = (uint32_t)__builtin_amdgcn_readlane((int)pr, qq * QG);
                 const int rsA = __builtin_amdgcn_readlane(sA, qq * QG), rsB = __builtin_amdgcn_readlane(sB, qq * QG);
                 const int rnewb = __builtin_amdgcn_readlane((int)gslow, qq * QG);
-                const uint32_t *rdA = s_cnt + (size_t)qq * 3 * Kpad, *rdB = rdA + Kpad, *rcN = rdB + Kpad;
+                const uint32_t *rcN = s_cnt + (size_t)qq * Kpad;
+                const int rsgA = A < rpr ? -1 : 1, rsgB = B < rpr ? -1 : 1;
+                auto rdA = [&](int k) { return upd_loss(rcN, k, K, W, nb - 1, rsgA, nb - 1, 0) + (same ? upd_loss(rcN, k, K, W, nb - 1, rsgA, nb - 1 - pk_shift, pk_sub) : 0u); };
+                auto rdB = [&](int k) { return upd_loss(rcN, k, K, W, nb - 1, rsgB, nb - 1 - pk_shift, pk_sub); };
                 if (rsA == SLOT_SLOW) {
                     const uint32_t lo = min(A, rpr), hi = max(A, rpr);
                     const int slot = table_find_from(c, pack_pair(lo, hi), hash_pair(lo, hi), 1);
                     if (slot >= 0) {
                         int gone = 0;
-                        table_update<SEEDED, WEIGHTED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdA[k]; }, false, &gone, dcw);
+                        table_update<SEEDED, WEIGHTED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdA(k); }, false, &gone, dcw);
                         if constexpr (STATS) deletes += (unsigned)gone, ++found;
                     }
                 }
@@ -2290,7 +2317,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const int slot = table_find_from(c, pack_pair(lo, hi), hash_pair(lo, hi), 1);
                     if (slot >= 0) {
                         int gone = 0;
-                        table_update<SEEDED, WEIGHTED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdB[k]; }, false, &gone, dcw);
+                        table_update<SEEDED, WEIGHTED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdB(k); }, false, &gone, dcw);
                         if constexpr (STATS) deletes += (unsigned)gone, ++found;
                     }
                 }

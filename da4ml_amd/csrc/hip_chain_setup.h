@@ -15,7 +15,8 @@ struct HipBackend::Impl {
     int n_lanes = 4;  // chain groups = greedy-loop streams.  Measured (C3 batch 64, loop ms): 2 -> 880, 3 -> 871, 4 -> 838, 5..8 -> 1470:
                       // four hardware queues; the poll stream's rare copies share one of them at no visible cost
     int upd_total_blocks = 2560;  // k_iter_update blocks over all chains of a batch (4 waves x 4 groups each); measured (C3 batch 64,
-                                  // solves/s): 1024: 45.3, 1536: 53.3, 2048: 53.8, 2560: 55.5, 4096: 47.5
+                                  // solves/s): 1024: 45.3, 1536: 53.3, 2048: 53.8, 2560: 55.5, 4096: 47.5; again with seven resident waves per SIMD
+                                  // (profiles/ab_update_register_diet.txt): 1792: 110.9, 2048: 112.8, 2304: 113.4, 2560: 113.2 - 113.7, 3072: 113.7, 3328: 113.0 -- flat around 2560
     DeviceBuffer arena, desc_buf, io_buf, gather_buf, piece_buf;  // gather_buf: the results of a batch, contiguous, before they leave
     unsigned int *d_done = nullptr;
     unsigned int *h_done = nullptr;  // pinned, two words: done counters of alternating poll windows
