@@ -485,8 +485,8 @@ struct Ctx {
 
 // ---- tie order of a chain.  SEEDED is a template parameter of every kernel that forms, compares or takes apart a tie word, as MANYCOL is of the
 // selection kernel: the unseeded instantiations are instruction for instruction what they were, a seeded chain pays one 48-bit multiply per word.
-// Every site goes through these four: a tie word formed one way and compared with one formed the other gives picks that are valid adder
-// graphs but not the maximum of the chain's order.
+// Every site goes through these three (the code that writes blocks: through the block evaluator below, which is built on them): a tie word
+// formed one way and compared with one formed the other gives picks that are valid adder graphs but not the maximum of the chain's order.
 template <bool SEEDED> __device__ __forceinline__ unsigned long long tie_of(uint32_t id0, uint32_t id1, int idx, unsigned long long seed) {
     if constexpr (SEEDED)
         return tie_word_seeded(id0, id1, idx, seed);
@@ -509,16 +509,38 @@ template <bool SEEDED> __device__ __forceinline__ uint32_t blk_pos(uint32_t k, u
 
 // ---- rank of a table entry.  WEIGHTED is a template parameter of the kernels that form ranks (k_init_pairs, k_iter_update), as SEEDED is: a chain
 // whose weight is its method's constant runs the instantiations that hold the constant as a literal -- register for register what they were --,
-// a chain with another weight carries its bits (`dcw`) in a scalar register: read from the descriptor with the other fields of the step, handed to
-// the table operations as an argument (the chain context stays what it was: the selection kernel, which forms no rank, is built from it too).
-// All four sites that form a rank go through this (table_insert, table_update, and in update_partners the side-by-side re-evaluation and the
-// block creation): one site left on the constant gives valid graphs whose picks depend on where a block lies in the table.
+// a chain with another weight carries its bits (`dcw`) in a scalar register: read from the descriptor with the other fields of the step, held by
+// the block evaluator below (the chain context stays what it was: the selection kernel, which forms no rank, is built from it too).
+// The evaluator is the only caller: a rank formed past it, on the constant, gives valid graphs whose picks depend on where a block lies in the table.
 template <bool WEIGHTED> __device__ __forceinline__ uint32_t rank_of(const Ctx &c, uint32_t dcw, uint32_t n, int ov, float dl) {
     if constexpr (WEIGHTED)
         return entry_rank(n, ov, dl, c.method, u2f(dcw));
     else
         return entry_rank(n, ov, dl, c.method);
 }
+
+// ---- block evaluator: how the counts of a pair block become its best entry.  Every code path that writes a block's counts (table_insert, table_update,
+// and in update_partners the side-by-side re-evaluation and the block creation) forms its candidates, keeps the best and takes it apart HERE, so the
+// chain's rank (weight) and tie order (seed) are threaded through one place.  It carries what a rank needs: the chain context and the weight bits.
+template <bool SEEDED, bool WEIGHTED> struct BlockEval {
+    const Ctx &c;
+    uint32_t dcw;  // bits of the chain's latency-penalty weight in the WEIGHTED instantiations, unused (0) in the others
+    // candidate word of key `k` with count `n` in a block of rows with overlap `ov`, latency difference `dl`: rank << 8 | position in the
+    // within-block order, 0 = not selectable
+    __device__ __forceinline__ unsigned long long candidate(uint32_t n, uint32_t k, int ov, float dl) const {
+        const uint32_t r = rank_of<WEIGHTED>(c, dcw, n, ov, dl);
+        return r ? (((unsigned long long)r << 8) | blk_pos<SEEDED>(k, c.seed)) : 0ull;
+    }
+    static __device__ __forceinline__ void fold(unsigned long long &best, unsigned long long cand) { best = cand > best ? cand : best; }
+    // a block's best candidate word (the maximum over its keys) -> rank and key index of its best entry
+    static __device__ __forceinline__ uint32_t rank_of_best(unsigned long long best) { return (uint32_t)(best >> 8); }
+    __device__ __forceinline__ uint32_t idx_of_best(unsigned long long best) const { return blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed); }
+    // tie word and bound word (0: nothing selectable) of the best entry (rank, idx) of the block of rows lo <= hi
+    __device__ __forceinline__ unsigned long long tie(uint32_t lo, uint32_t hi, uint32_t idx) const { return tie_of<SEEDED>(lo, hi, (int)idx, c.seed); }
+    __device__ __forceinline__ unsigned long long word(uint32_t lo, uint32_t hi, uint32_t rank, uint32_t idx) const {
+        return rank ? bound_word(rank, tie(lo, hi, idx)) : 0ull;
+    }
+};
 
 // launch_id: 2 * iteration for k_iter_select2, 2 * iteration + 1 for k_iter_update (only the low two bits are used)
 template <bool SEEDED = false> __device__ __forceinline__ Ctx make_ctx_raw(ChainDev *g, int launch_id) {
@@ -644,15 +666,30 @@ __device__ __forceinline__ void fold_entry(const Ctx &c, uint32_t rank, unsigned
 // group in one round trip; the copy in the payload header is what the update kernel reads with the counts)
 __device__ __forceinline__ DA_GLOBAL uint8_t *hidx_ptr(const Ctx &c) { return reinterpret_cast<DA_GLOBAL uint8_t *>(c.hrank + ((size_t)c.cmask + 1)); }
 
+// one lane: publish a block just created in `slot` (its counts are stored by the lanes that hold them) -- header, rank and best-key index, the
+// group's bound, the candidate list of the next pick.  `best`: the block's best candidate word
+template <bool SEEDED, bool WEIGHTED>
+__device__ __forceinline__ void publish_new_block(const BlockEval<SEEDED, WEIGHTED> &ev, int slot, uint32_t lo, uint32_t hi, int ov, float dl, unsigned long long best) {
+    const Ctx &c = ev.c;
+    const uint32_t rank = ev.rank_of_best(best), idx = ev.idx_of_best(best);
+    store_hdr(c, slot, ov, dl, rank, idx);
+    c.hrank[slot] = rank;
+    hidx_ptr(c)[slot] = (uint8_t)idx;
+    if (rank) {  // (the tie word is spelled at both uses: held in a variable it costs the SEEDED instantiations of k_iter_update two more VGPRs)
+        group_note(c, slot, 0ull, bound_word(rank, ev.tie(lo, hi, idx)));
+        fold_entry(c, rank, ev.tie(lo, hi, idx));
+    }
+}
+
 // Store a complete block.  cnt_of(k) gives the count of key k; returns false when the table is full.
 // Precondition: at least one count >= 2 (checked by the caller), key absent.  ra / rb: intervals of rows lo / hi.
-// `w_out` (optional): the bound word of the new block's best entry, 0 when none is selectable (wave-uniform).
 // `tally`: count the new block in the chain's n_live here, with a device atomic.  k_iter_update passes false and adds its creations and deletions
 // ONCE PER WORKGROUP: in the first thousands of steps of a chain hundreds of blocks are created and deleted per step, and one atomic each on the
 // same line of the chain descriptor serialises in the L2 at ~12 ns apiece -- behind which every later load of the issuing wave waits (vmcnt is
 // in-order): measured in round 6, k_iter_update of steps 0 - 2000 took 24.8 us for one chain where the late steps take 6.7.
-template <bool SEEDED = false, bool WEIGHTED = false, class CntFn>
-__device__ bool table_insert(const Ctx &c, uint32_t lo, uint32_t hi, const RowInfo &ra, const RowInfo &rb, CntFn cnt_of, unsigned long long *w_out = nullptr, bool tally = true, uint32_t dcw = 0) {
+template <bool SEEDED, bool WEIGHTED, class CntFn>
+__device__ bool table_insert(const BlockEval<SEEDED, WEIGHTED> &ev, uint32_t lo, uint32_t hi, const RowInfo &ra, const RowInfo &rb, CntFn cnt_of, bool tally = true) {
+    const Ctx &c = ev.c;
     int lane = lane_id();
     unsigned long long key = pack_pair(lo, hi);
     int slot = table_claim(c, key, hash_pair(lo, hi));
@@ -668,35 +705,23 @@ __device__ bool table_insert(const Ctx &c, uint32_t lo, uint32_t hi, const RowIn
         uint32_t n = k < c.K ? cnt_of(k) : 0u;
         if (n > 65535u) c.g->error = E_COUNT_OVERFLOW;
         cnt[k] = (uint16_t)n;
-        uint32_t r = rank_of<WEIGHTED>(c, dcw, n, ov, dl);
-        unsigned long long cand = r ? (((unsigned long long)r << 8) | blk_pos<SEEDED>((unsigned)k, c.seed)) : 0ull;
-        best = cand > best ? cand : best;
+        ev.fold(best, ev.candidate(n, (uint32_t)k, ov, dl));
     }
     best = wave_max_u64(best);
-    if (w_out) *w_out = (best >> 8) ? bound_word((uint32_t)(best >> 8), tie_of<SEEDED>(lo, hi, (int)blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed), c.seed)) : 0ull;
     if (lane == 0) {
-        uint32_t rank = (uint32_t)(best >> 8), idx = blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed);
-        store_hdr(c, slot, ov, dl, rank, idx);
-        c.hrank[slot] = rank;
-        hidx_ptr(c)[slot] = (uint8_t)idx;
-        if (rank) {
-            group_note(c, slot, 0ull, bound_word(rank, tie_of<SEEDED>(lo, hi, (int)idx, c.seed)));
-            fold_entry(c, rank, tie_of<SEEDED>(lo, hi, (int)idx, c.seed));
-        }
+        publish_new_block(ev, slot, lo, hi, ov, dl, best);
         if (tally) atomicAdd(&c.g->n_live, 1u);  // no return value: fire-and-forget (the peak is sampled by the selection)
     }
     return true;
 }
 
-// lane 0: publish the re-evaluated best key of a block (or delete the block when no count >= 2 is left)
-// bound word of a block's best entry as its header holds it
-template <bool SEEDED = false> __device__ __forceinline__ unsigned long long hdr_word(unsigned long long key, uint32_t rank, uint32_t idx, unsigned long long seed) {
-    return rank ? bound_word(rank, tie_of<SEEDED>((uint32_t)key, (uint32_t)(key >> 32), (int)idx, seed)) : 0ull;
-}
-// `best`: the block's maximum of (rank << 8 | position in the within-block order), 0 = nothing selectable
-template <bool SEEDED = false>
-__device__ __forceinline__ void block_commit(const Ctx &c, int slot, unsigned long long key, const BlkHdr &h, unsigned long long best, int alive, bool tally = true) {
-    const unsigned long long w_old = hdr_word<SEEDED>(key, h.rank, h.idx, c.seed);
+// one lane: publish the re-evaluated best key of a block (or delete the block when no count >= 2 is left)
+// `best`: the block's best candidate word, 0 = nothing selectable
+template <bool SEEDED, bool WEIGHTED>
+__device__ __forceinline__ void block_commit(const BlockEval<SEEDED, WEIGHTED> &ev, int slot, unsigned long long key, const BlkHdr &h, unsigned long long best, int alive, bool tally = true) {
+    const Ctx &c = ev.c;
+    const uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32);
+    const unsigned long long w_old = ev.word(lo, hi, h.rank, h.idx);  // bound word of the block's best entry as its header holds it
     if (!alive) {
         c.hrank[slot] = 0;
         c.hkey[slot] = c.tomb;
@@ -704,19 +729,18 @@ __device__ __forceinline__ void block_commit(const Ctx &c, int slot, unsigned lo
         if (h.rank) group_note(c, slot, w_old, 0ull);
         return;
     }
-    const uint32_t rank = (uint32_t)(best >> 8), idx = blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed);
+    const uint32_t rank = ev.rank_of_best(best), idx = ev.idx_of_best(best);
     if (rank != h.rank) c.hrank[slot] = rank;
     if (rank != h.rank || idx != h.idx) store_best(c, slot, rank, idx);
     if (idx != h.idx) hidx_ptr(c)[slot] = (uint8_t)idx;
-    if (rank != h.rank || (rank && idx != h.idx))
-        group_note(c, slot, w_old, rank ? bound_word(rank, tie_of<SEEDED>((uint32_t)key, (uint32_t)(key >> 32), (int)idx, c.seed)) : 0ull);
-    if (rank) fold_entry(c, rank, tie_of<SEEDED>((uint32_t)key, (uint32_t)(key >> 32), (int)idx, c.seed));  // changed or not: the block touches a row of the step
+    if (rank != h.rank || (rank && idx != h.idx)) group_note(c, slot, w_old, ev.word(lo, hi, rank, idx));
+    if (rank) fold_entry(c, rank, ev.tie(lo, hi, idx));  // changed or not: the block touches a row of the step
 }
 
-// Re-evaluate a block after its counts changed (new_cnt(k, old) -> new count); deletes it when no count >= 2.
-// Returns the bound word of the block's best entry afterwards (0: deleted, or nothing selectable); wave-uniform.
-template <bool SEEDED = false, bool WEIGHTED = false, class CntFn>
-__device__ unsigned long long table_update(const Ctx &c, int slot, unsigned long long key, CntFn new_cnt, bool tally = true, int *deleted = nullptr, uint32_t dcw = 0) {
+// Re-evaluate a block after its counts changed (new_cnt(k, old) -> new count); deletes it when no count >= 2 is left and returns true then (wave-uniform).
+template <bool SEEDED, bool WEIGHTED, class CntFn>
+__device__ bool table_update(const BlockEval<SEEDED, WEIGHTED> &ev, int slot, unsigned long long key, CntFn new_cnt, bool tally = true) {
+    const Ctx &c = ev.c;
     int lane = lane_id();
     const BlkHdr h = load_hdr(c, slot);
     DA_GLOBAL uint16_t *cnt = blk_cnt(c, slot);
@@ -727,15 +751,49 @@ __device__ unsigned long long table_update(const Ctx &c, int slot, unsigned long
         uint32_t n = new_cnt(k, old);
         if (n != old) cnt[k] = (uint16_t)n;
         alive |= n >= 2;
-        uint32_t r = rank_of<WEIGHTED>(c, dcw, n, h.ov, h.dl);
-        unsigned long long cand = r ? (((unsigned long long)r << 8) | blk_pos<SEEDED>((unsigned)k, c.seed)) : 0ull;
-        best = cand > best ? cand : best;
+        ev.fold(best, ev.candidate(n, (uint32_t)k, h.ov, h.dl));
     }
     best = wave_max_u64(best);
     alive = __any(alive);
-    if (lane == 0) block_commit<SEEDED>(c, slot, key, h, best, alive, tally);
-    if (deleted) *deleted = !alive;
-    return alive && (best >> 8) ? bound_word((uint32_t)(best >> 8), tie_of<SEEDED>((uint32_t)key, (uint32_t)(key >> 32), (int)blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed), c.seed)) : 0ull;
+    if (lane == 0) block_commit(ev, slot, key, h, best, alive, tally);
+    return !alive;
+}
+
+// one wave: a block exists while one of its counts is >= 2.  `cnt`: a count vector wherever it lies (LDS or global u32, an int32 slab of a sharded chain)
+template <class CntPtr> __device__ __forceinline__ bool wave_any_ge2(CntPtr cnt, int K) {
+    int f = 0;
+    for (int k = lane_id(); k < K; k += WAVE) f |= cnt[k] >= 2;
+    return __any(f);
+}
+
+// The six pairs among the rows a step modified -- A, B and the new row N --, by the row of the exact count vectors the substitution leaves for them
+// (sp_cnt; the head of a sharded chain's slab): (A,A) (A,B) (B,B) (A,N) (B,N) (N,N).  `existed`: the pair may have a block already (the ones with N
+// are new); `active`: the pair is one of its own (when the pick is a row with itself, those with B repeat those with A).
+struct SpecialPair {
+    uint32_t lo, hi;
+    bool existed, active;
+};
+__device__ __forceinline__ SpecialPair special_pair(int row, uint32_t A, uint32_t B, uint32_t Nw) {
+    const bool same = A == B;
+    switch (row) {
+    case 0: return SpecialPair{A, A, true, true};
+    case 1: return SpecialPair{A, B, true, !same};
+    case 2: return SpecialPair{B, B, true, !same};
+    case 3: return SpecialPair{A, Nw, false, true};
+    case 4: return SpecialPair{B, Nw, false, !same};
+    default: return SpecialPair{Nw, Nw, false, true};
+    }
+}
+// One wave: the block of such a pair is replaced by its exact counts `cnt` -- re-counted where it exists (deleted when no count >= 2 is left),
+// created where it does not and a count reaches 2.  ra / rb: records of rows lo / hi.  Either way the block's best entry is passed to fold_entry.
+template <bool SEEDED, bool WEIGHTED, class CntPtr>
+__device__ __forceinline__ void replace_block(const BlockEval<SEEDED, WEIGHTED> &ev, const SpecialPair &p, const RowInfo &ra, const RowInfo &rb, CntPtr cnt) {
+    const unsigned long long key = pack_pair(p.lo, p.hi);
+    const int slot = p.existed ? table_find(ev.c, key, hash_pair(p.lo, p.hi)) : -1;
+    if (slot >= 0)
+        table_update(ev, slot, key, [&](int k, uint32_t) { return (uint32_t)cnt[k]; });
+    else if (wave_any_ge2(cnt, ev.c.K))
+        table_insert(ev, p.lo, p.hi, ra, rb, [&](int k) { return (uint32_t)cnt[k]; });
 }
 
 // ------------------------------------------------------------------------------------------------ k_prepare
@@ -874,10 +932,12 @@ __device__ __forceinline__ void count_row_pair(const Ctx &c, const typename RowF
     }
     lds_fence();
 }
-__device__ __forceinline__ bool wave_any_ge2(const uint32_t *cnt, int K) {
-    int f = 0;
-    for (int k = lane_id(); k < K; k += WAVE) f |= cnt[k] >= 2;
-    return __any(f);
+// one wave per pair of input rows: pair index p = hi (hi + 1) / 2 + lo  ->  (lo, hi), lo <= hi
+__device__ __forceinline__ void pair_of_index(long long p, uint32_t &lo, uint32_t &hi) {
+    long long i1 = (long long)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
+    while (i1 * (i1 + 1) / 2 > p) --i1;
+    while ((i1 + 1) * (i1 + 2) / 2 <= p) ++i1;
+    hi = (uint32_t)i1, lo = (uint32_t)(p - i1 * (i1 + 1) / 2);
 }
 
 // ------------------------------------------------------------------------------------------------ k_init_pairs
@@ -892,11 +952,8 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __global__ voi
     long long n_pairs = n_in * (n_in + 1) / 2;
     long long p = (long long)blockIdx.x * (blockDim.x / WAVE) + wave_id();
     if (p >= n_pairs) return;
-    // p = i1 (i1 + 1) / 2 + i0
-    long long i1 = (long long)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
-    while (i1 * (i1 + 1) / 2 > p) --i1;
-    while ((i1 + 1) * (i1 + 2) / 2 <= p) ++i1;
-    uint32_t hi = (uint32_t)i1, lo = (uint32_t)(p - i1 * (i1 + 1) / 2);
+    uint32_t lo, hi;
+    pair_of_index(p, lo, hi);
     const auto *rl = reinterpret_cast<const typename RowFmt<Cell>::Entry *>(g->rlist);
     count_row_pair<Cell>(c, rl, lo, hi, cnt);
     if (!wave_any_ge2(cnt, c.K)) return;
@@ -904,7 +961,7 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __global__ voi
         if (lane_id() == 0) g->unknown_hit = 1;
         return;
     }
-    table_insert<SEEDED, WEIGHTED>(c, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; }, nullptr, true, WEIGHTED ? f2u(g->dc_weight) : 0u);
+    table_insert(BlockEval<SEEDED, WEIGHTED>{c, WEIGHTED ? f2u(g->dc_weight) : 0u}, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; });
 }
 
 // ================================================================================= k_iter_select2: the next pick, one step ahead
@@ -2016,6 +2073,15 @@ __device__ __forceinline__ uint32_t upd_loss(const uint32_t *cN, int k, int K, i
     const int sg = k >= W, t = __mul24(k - (sg ? W : 0) - nbm1, sgn) + cst;
     return (k < K && (unsigned)t < (unsigned)W) ? cN[((sg ^ sub) ? W : 0) + t] : 0u;
 }
+// What key k of the block (X, partner) loses with the partner's digit pairs counted in cN.  `role_b`: X is B -- the B-role pairs --, else X is A:
+// the A-role pairs, and the B-role ones too when the pick is a row with itself (`same`; B has no block of its own then).  `above`: the partner
+// lies above X (the key is mirrored).  nb, K: the chain's; shift, sub: the pick's key.
+__device__ __forceinline__ uint32_t block_loss(const uint32_t *cN, int k, bool role_b, bool above, bool same, int K, int nb, int shift, int sub) {
+    const int W = 2 * nb - 1, sgn = above ? -1 : 1;
+    uint32_t v = upd_loss(cN, k, K, W, nb - 1, sgn, role_b ? nb - 1 - shift : nb - 1, role_b ? sub : 0);
+    if (same) v += upd_loss(cN, k, K, W, nb - 1, sgn, nb - 1 - shift, sub);
+    return v;
+}
 
 // update_partners: ONE WAVEFRONT works through the partner rows first + q, first + stride + q, ... < limit of the step (q = its
 // four 16-lane groups); no block-level synchronisation inside.  `ref_next` = the (pre-fetched) reference of this group's first
@@ -2029,7 +2095,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
     using Entry = typename F::Entry;
     constexpr int HW = ((sizeof(Cell) == 4 ? 24 : 60) + HL - 1) / HL;  // count words per lane (a block's words over its HL lanes): narrow layout Kpad / 2 <= 24 words, wide <= 60
     const Ctx &c = u.c;
-    const uint32_t dcw = u.dcw;
+    const BlockEval<SEEDED, WEIGHTED> ev{c, u.dcw};
     const uint32_t A = u.A, B = u.B, Nw = u.Nw;
     const int m = u.m, n_in = u.n_in, pk_shift = u.shift, pk_sub = u.sub;
     const DA_GLOBAL Entry *rl = u.rl;
@@ -2183,12 +2249,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
             // this lane's block loses the A-role pairs (lower half: A's block) or the B-role ones (upper half: B's block) -- and both when
             // the pick is a row with itself (A's block; the upper half then has no block)
             const uint32_t rowX = half ? B : A;
-            const int sgnX = rowX < pr ? -1 : 1, cstX = half ? nb - 1 - pk_shift : nb - 1, subX = half ? pk_sub : 0;
-            auto lost = [&](int k) {
-                uint32_t v = upd_loss(cN, k, K, W, nb - 1, sgnX, cstX, subX);
-                if (same) v += upd_loss(cN, k, K, W, nb - 1, sgnX, nb - 1 - pk_shift, pk_sub);
-                return v;
-            };
+            auto lost = [&](int k) { return block_loss(cN, k, half != 0, rowX < pr, same, K, nb, pk_shift, pk_sub); };
             unsigned long long best = 0;
             int alive = 0;
 #pragma unroll
@@ -2199,16 +2260,14 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const uint32_t n0 = o0 - lost(2 * j), n1 = o1 - lost(2 * j + 1);
                     if (n0 != o0 || n1 != o1) reinterpret_cast<DA_GLOBAL uint32_t *>(blk_ptr(c, sX) + 16)[j] = (n0 & 0xFFFFu) | (n1 << 16);
                     alive |= (n0 >= 2u) | (n1 >= 2u);
-                    const uint32_t r0 = rank_of<WEIGHTED>(c, dcw, n0, ov, dl), r1 = rank_of<WEIGHTED>(c, dcw, n1, ov, dl);
-                    const unsigned long long c0 = r0 ? (((unsigned long long)r0 << 8) | blk_pos<SEEDED>((unsigned)(2 * j), c.seed)) : 0ull;
-                    const unsigned long long c1 = r1 ? (((unsigned long long)r1 << 8) | blk_pos<SEEDED>((unsigned)(2 * j + 1), c.seed)) : 0ull;
-                    best = c0 > best ? c0 : best;
-                    best = c1 > best ? c1 : best;
+                    const unsigned long long c0 = ev.candidate(n0, (uint32_t)(2 * j), ov, dl), c1 = ev.candidate(n1, (uint32_t)(2 * j + 1), ov, dl);
+                    ev.fold(best, c0);
+                    ev.fold(best, c1);
                 }
             }
             best = part_row_max_u64<HL>(best);  // all lanes take part (the DPP source lanes must be active); every lane of a block's HL holds its result
             const bool any_alive = (((uint32_t)(__ballot(alive != 0) >> (qsh + HL * half)) & HMASK) != 0);
-            if (has && hl == HL - 1) block_commit<SEEDED>(c, sX, pack_pair(min(rowX, pr), max(rowX, pr)), BlkHdr{ov, dl, (uint32_t)hdX.z, (uint32_t)hdX.w}, best, any_alive, false);
+            if (has && hl == HL - 1) block_commit(ev, sX, pack_pair(min(rowX, pr), max(rowX, pr)), BlkHdr{ov, dl, (uint32_t)hdX.z, (uint32_t)hdX.w}, best, any_alive, false);
             if constexpr (STATS) deletes += (unsigned)__popcll(__ballot(has && hl == HL - 1 && !any_alive));  // (wave-uniform: the blocks this pass deleted, tallied once per workgroup)
         }
         UPD_TIMER_MARK(3)  // block updates
@@ -2268,25 +2327,14 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const uint32_t n0 = cN[2 * j], n1 = cN[2 * j + 1];  // (zero beyond K: nothing ever counts there)
                     if ((n0 | n1) > 65535u) c.g->error = E_COUNT_OVERFLOW;
                     reinterpret_cast<DA_GLOBAL uint32_t *>(blk_ptr(c, nslot) + 16)[j] = (n0 & 0xFFFFu) | (n1 << 16);
-                    const uint32_t r0 = rank_of<WEIGHTED>(c, dcw, n0, ovn, dln), r1 = rank_of<WEIGHTED>(c, dcw, n1, ovn, dln);
-                    const unsigned long long c0 = r0 ? (((unsigned long long)r0 << 8) | blk_pos<SEEDED>((unsigned)(2 * j), c.seed)) : 0ull;
-                    const unsigned long long c1 = r1 ? (((unsigned long long)r1 << 8) | blk_pos<SEEDED>((unsigned)(2 * j + 1), c.seed)) : 0ull;
-                    bestn = c0 > bestn ? c0 : bestn;
-                    bestn = c1 > bestn ? c1 : bestn;
+                    const unsigned long long c0 = ev.candidate(n0, (uint32_t)(2 * j), ovn, dln), c1 = ev.candidate(n1, (uint32_t)(2 * j + 1), ovn, dln);
+                    ev.fold(bestn, c0);
+                    ev.fold(bestn, c1);
                 }
             }
             bestn = part_row_max_u64<8>(bestn);  // (eight lanes, then the two halves of the group)
             if constexpr (QG == 16) bestn = dpp_max_u64<0x140, 0xF>(bestn);  // row_mirror: lane i <-> 15 - i
-            if (made && l == QG - 1) {
-                const uint32_t rank = (uint32_t)(bestn >> 8), bidx = blk_pos<SEEDED>((uint32_t)(bestn & 0xFF), c.seed);
-                store_hdr(c, nslot, ovn, dln, rank, bidx);
-                c.hrank[nslot] = rank;
-                hidx_ptr(c)[nslot] = (uint8_t)bidx;
-                if (rank) {
-                    group_note(c, nslot, 0ull, bound_word(rank, tie_of<SEEDED>(pr, Nw, (int)bidx, c.seed)));
-                    fold_entry(c, rank, tie_of<SEEDED>(pr, Nw, (int)bidx, c.seed));
-                }
-            }
+            if (made && l == QG - 1) publish_new_block(ev, nslot, pr, Nw, ovn, dln, bestn);
             if constexpr (STATS) inserts += (unsigned)__popcll(__ballot(made && l == 0));
         }
         // ---- rare: blocks beyond their first bucket (look-up, or creation in a full bucket) -- the whole wave, one group at a time
@@ -2300,15 +2348,13 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                 const int rsA = __builtin_amdgcn_readlane(sA, qq * QG), rsB = __builtin_amdgcn_readlane(sB, qq * QG);
                 const int rnewb = __builtin_amdgcn_readlane((int)gslow, qq * QG);
                 const uint32_t *rcN = s_cnt + (size_t)qq * Kpad;
-                const int rsgA = A < rpr ? -1 : 1, rsgB = B < rpr ? -1 : 1;
-                auto rdA = [&](int k) { return upd_loss(rcN, k, K, W, nb - 1, rsgA, nb - 1, 0) + (same ? upd_loss(rcN, k, K, W, nb - 1, rsgA, nb - 1 - pk_shift, pk_sub) : 0u); };
-                auto rdB = [&](int k) { return upd_loss(rcN, k, K, W, nb - 1, rsgB, nb - 1 - pk_shift, pk_sub); };
+                auto rdA = [&](int k) { return block_loss(rcN, k, false, A < rpr, same, K, nb, pk_shift, pk_sub); };
+                auto rdB = [&](int k) { return block_loss(rcN, k, true, B < rpr, same, K, nb, pk_shift, pk_sub); };
                 if (rsA == SLOT_SLOW) {
                     const uint32_t lo = min(A, rpr), hi = max(A, rpr);
                     const int slot = table_find_from(c, pack_pair(lo, hi), hash_pair(lo, hi), 1);
                     if (slot >= 0) {
-                        int gone = 0;
-                        table_update<SEEDED, WEIGHTED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdA(k); }, false, &gone, dcw);
+                        const bool gone = table_update(ev, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdA(k); }, false);
                         if constexpr (STATS) deletes += (unsigned)gone, ++found;
                     }
                 }
@@ -2316,13 +2362,12 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const uint32_t lo = min(B, rpr), hi = max(B, rpr);
                     const int slot = table_find_from(c, pack_pair(lo, hi), hash_pair(lo, hi), 1);
                     if (slot >= 0) {
-                        int gone = 0;
-                        table_update<SEEDED, WEIGHTED>(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdB(k); }, false, &gone, dcw);
+                        const bool gone = table_update(ev, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - rdB(k); }, false);
                         if constexpr (STATS) deletes += (unsigned)gone, ++found;
                     }
                 }
                 if (rnewb) {
-                    table_insert<SEEDED, WEIGHTED>(c, rpr, Nw, load_row(c.rows, rpr), rnew, [&](int k) { return rcN[k]; }, nullptr, false, dcw);
+                    table_insert(ev, rpr, Nw, load_row(c.rows, rpr), rnew, [&](int k) { return rcN[k]; }, false);
                     if constexpr (STATS) ++inserts;
                 }
             }
@@ -2343,38 +2388,18 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
 template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __forceinline__ void special_pairs(ChainDev *gq, const UpdStep<Cell> &u, int part) {
     const Ctx &c = u.c;
     const uint32_t A = u.A, B = u.B, Nw = u.Nw;
-    const bool same = A == B;
+    const BlockEval<SEEDED, WEIGHTED> ev{c, u.dcw};
     const DA_GLOBAL uint32_t *spc = (const DA_GLOBAL uint32_t *)gq->sp_cnt;
     const RowInfo ra = load_row(c.rows, A), rb = load_row(c.rows, B), rn = load_row(c.rows, Nw);
     const int lane = lane_id();
     for (int sp = part * UPD_WAVES + wave_id(); sp < min(6, (part + 1) * UPD_WAVES); sp += UPD_WAVES) {
-        uint32_t lo = A, hi = A;
-        bool active = true, existed = false;
-        int row = 0;  // row of the count vectors left by the substitution block: (A,A) (A,B) (B,B) (A,N) (B,N) (N,N)
-        switch (sp) {
-        case 0: lo = A, hi = A, existed = true, row = 0; break;
-        case 1: lo = A, hi = B, existed = true, active = !same, row = 1; break;
-        case 2: lo = A, hi = Nw, row = 3; break;
-        case 3: lo = B, hi = B, existed = true, active = !same, row = 2; break;
-        case 4: lo = B, hi = Nw, active = !same, row = 4; break;
-        default: lo = Nw, hi = Nw, row = 5; break;
-        }
-        if (!active) continue;
-        const DA_GLOBAL uint32_t *cnt = spc + (size_t)row * c.Kpad;
-        const unsigned long long key = pack_pair(lo, hi);
-        const int slot = existed ? table_find(c, key, hash_pair(lo, hi)) : -1;
-        unsigned long long w = 0;
-        if (slot >= 0)
-            w = table_update<SEEDED, WEIGHTED>(c, slot, key, [&](int k, uint32_t) { return cnt[k]; }, true, nullptr, u.dcw);
-        else {
-            int f = 0;
-            for (int k = lane; k < c.K; k += WAVE) f |= cnt[k] >= 2u;
-            if (__any(f)) {
-                const RowInfo xa = pick_row(lo == Nw, rn, pick_row(lo == A, ra, rb)), xb = pick_row(hi == Nw, rn, pick_row(hi == A, ra, rb));
-                table_insert<SEEDED, WEIGHTED>(c, lo, hi, xa, xb, [&](int k) { return cnt[k]; }, &w, true, u.dcw);
-            }
-        }
-        (void)w;  // (both paths have passed the block's best entry to fold_entry)
+        // this kernel's wave order 0 1 3 2 4 5 of the rows of special_pair: the four pairs with A, then (B,N), (N,N).  (Spelled as selects: an order array
+        // indexed by the wave becomes a load from constant memory in front of the longest dependent chain of the kernel)
+        const int row = sp == 2 ? 3 : sp == 3 ? 2 : sp;
+        const SpecialPair p = special_pair(row, A, B, Nw);
+        if (!p.active) continue;
+        const RowInfo xa = pick_row(p.lo == Nw, rn, pick_row(p.lo == A, ra, rb)), xb = pick_row(p.hi == Nw, rn, pick_row(p.hi == A, ra, rb));
+        replace_block(ev, p, xa, xb, spc + (size_t)row * c.Kpad);
     }
     // the entries the search listed (they touch exactly one of A / B and reach the untouched entry): a block whose other row is a partner
     // row is re-evaluated by the partner waves of this launch, which pass its best entry on themselves; the others are unchanged -- passed on here.
@@ -2475,10 +2500,8 @@ template <class Cell> __global__ void __launch_bounds__(256) k_cs_init_counts(Ch
     const long long n_in = g->n_in, n_pairs = n_in * (n_in + 1) / 2;
     const long long p = (long long)blockIdx.x * (blockDim.x / WAVE) + wave_id();
     if (p >= n_pairs) return;
-    long long i1 = (long long)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
-    while (i1 * (i1 + 1) / 2 > p) --i1;
-    while ((i1 + 1) * (i1 + 2) / 2 <= p) ++i1;
-    const uint32_t hi = (uint32_t)i1, lo = (uint32_t)(p - i1 * (i1 + 1) / 2);
+    uint32_t lo, hi;
+    pair_of_index(p, lo, hi);
     count_row_pair<Cell>(c, reinterpret_cast<const typename RowFmt<Cell>::Entry *>(g->rlist), lo, hi, cnt);
     for (int k = lane_id(); k < c.K; k += WAVE) g->cs_init[(size_t)p * c.K + k] = (int32_t)cnt[k];
 }
@@ -2488,19 +2511,15 @@ template <class Cell> __global__ void __launch_bounds__(256) k_cs_init_table(Cha
     const long long n_in = g->n_in, n_pairs = n_in * (n_in + 1) / 2;
     const long long p = (long long)blockIdx.x * (blockDim.x / WAVE) + wave_id();
     if (p >= n_pairs) return;
-    long long i1 = (long long)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
-    while (i1 * (i1 + 1) / 2 > p) --i1;
-    while ((i1 + 1) * (i1 + 2) / 2 <= p) ++i1;
-    const uint32_t hi = (uint32_t)i1, lo = (uint32_t)(p - i1 * (i1 + 1) / 2);
+    uint32_t lo, hi;
+    pair_of_index(p, lo, hi);
     const int32_t *cnt = g->cs_init + (size_t)p * c.K;
-    int f = 0;
-    for (int k = lane_id(); k < c.K; k += WAVE) f |= cnt[k] >= 2;
-    if (!__any(f)) return;
+    if (!wave_any_ge2(cnt, c.K)) return;
     if (c.method < 0) {  // unknown method string with a non-empty table: the reference throws here
         if (lane_id() == 0) g->unknown_hit = 1;
         return;
     }
-    table_insert(c, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return (uint32_t)cnt[k]; });
+    table_insert(BlockEval<false, false>{c, 0u}, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return (uint32_t)cnt[k]; });
 }
 
 // one block: union of the partner rows of all ranks (summed flag fields != 0), ascending row ids -> cs_uni, cs_nuni
@@ -2607,6 +2626,7 @@ template <class Cell> __global__ void __launch_bounds__(256) k_cs_apply(ChainDev
     c.rword = g->spec[(g->iter - 1) & 1].word;
     c.cn = &g->c_n[(g->iter - 1) & 1];
     c.cl = &g->c_list[(g->iter - 1) & 1][0];
+    const BlockEval<false, false> ev{c, 0u};  // (the sharded kernels have no SEEDED / WEIGHTED instantiations)
     const int K = c.K;
     const int w = (int)blockIdx.x * 4 + wave_id();
     const uint32_t A = g->A, B = g->B, Nw = g->Nw;
@@ -2620,33 +2640,15 @@ template <class Cell> __global__ void __launch_bounds__(256) k_cs_apply(ChainDev
         if (lane_id() == 0)
             for (int e = 0; e < nl; ++e) {
                 const unsigned long long tw = ll[e].tie;
-                const uint32_t i0 = (uint32_t)((tw >> 7) & 0xFFFFFFu), i1 = (uint32_t)(tw >> 31);
+                uint32_t i0, i1;
+                tie_rows<false>(tw, c.seed, i0, i1);
                 const uint32_t r = (i0 == A || i0 == B) ? i1 : i0;
                 if (((g->cs_flags[r >> 2] >> (8 * (r & 3))) & 0xFF) == 0) fold_entry(c, (uint32_t)ll[e].rank, tw);
             }
     }
-    if (w < 6) {
-        uint32_t lo = A, hi = A;
-        bool active = true, existed = false;
-        switch (w) {
-        case 0: lo = A, hi = A, existed = true; break;
-        case 1: lo = A, hi = B, existed = true, active = !same; break;
-        case 2: lo = B, hi = B, existed = true, active = !same; break;
-        case 3: lo = A, hi = Nw; break;
-        case 4: lo = B, hi = Nw, active = !same; break;
-        default: lo = Nw, hi = Nw; break;
-        }
-        if (!active) return;
-        const int32_t *cnt = g->cs_slab + (size_t)w * K;
-        const unsigned long long key = pack_pair(lo, hi);
-        const int slot = existed ? table_find(c, key, hash_pair(lo, hi)) : -1;
-        if (slot >= 0)
-            table_update(c, slot, key, [&](int k, uint32_t) { return (uint32_t)cnt[k]; });
-        else {
-            int f = 0;
-            for (int k = lane_id(); k < K; k += WAVE) f |= cnt[k] >= 2;
-            if (__any(f)) table_insert(c, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return (uint32_t)cnt[k]; });
-        }
+    if (w < 6) {  // slab row w = count vector w of special_pair
+        const SpecialPair p = special_pair(w, A, B, Nw);
+        if (p.active) replace_block(ev, p, load_row(c.rows, p.lo), load_row(c.rows, p.hi), g->cs_slab + (size_t)w * K);
         return;
     }
     const int u = w - 6;
@@ -2656,16 +2658,14 @@ template <class Cell> __global__ void __launch_bounds__(256) k_cs_apply(ChainDev
     {
         const uint32_t lo = min(A, r), hi = max(A, r);
         const int slot = table_find(c, pack_pair(lo, hi), hash_pair(lo, hi));
-        if (slot >= 0) table_update(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - (uint32_t)dA[k]; });
+        if (slot >= 0) table_update(ev, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - (uint32_t)dA[k]; });
     }
     if (!same) {
         const uint32_t lo = min(B, r), hi = max(B, r);
         const int slot = table_find(c, pack_pair(lo, hi), hash_pair(lo, hi));
-        if (slot >= 0) table_update(c, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - (uint32_t)dB[k]; });
+        if (slot >= 0) table_update(ev, slot, pack_pair(lo, hi), [&](int k, uint32_t old) { return old - (uint32_t)dB[k]; });
     }
-    int f = 0;
-    for (int k = lane_id(); k < K; k += WAVE) f |= cN[k] >= 2;
-    if (__any(f)) table_insert(c, r, Nw, load_row(c.rows, r), load_row(c.rows, Nw), [&](int k) { return (uint32_t)cN[k]; });
+    if (wave_any_ge2(cN, K)) table_insert(ev, r, Nw, load_row(c.rows, r), load_row(c.rows, Nw), [&](int k) { return (uint32_t)cN[k]; });
     if (lane_id() == 0) atomicAdd(&g->st_partners, 1ull);
 }
 

@@ -1,6 +1,6 @@
 """The latency-penalty-weight cases that tests/golden/make_dc_weight_golden.py records with a patched copy of the restatement (oracle/cmvm_oracle.cc
 with its two constants made a variable) and that tests/test_emulated_dc_weight.py / tests/test_dc_weight_gpu.py replay: the smallest shapes at
-which each site that forms a rank and each layout runs.
+which each path that writes a block through the engine's block evaluator -- the one place that forms a rank -- and each layout runs.
 
 name -> (int_matrix arguments, options without the methods, methods, weights); weight None = unset (the method's own constant).
   narrow16   narrow entries, one chain per point: table_insert of k_init_pairs, the side-by-side re-evaluation and the block creation of k_iter_update

@@ -206,14 +206,20 @@ def retry():
 
 
 def shard_single():
-    """the column-sharded engine (k_cs_* kernels, k_iter_select2<Cell, SHARDED>) with one rank: exchanges are no-ops"""
+    """the column-sharded engine (k_cs_* kernels, k_iter_select2<Cell, SHARDED>) with one rank: exchanges are no-ops.  The last case (12x10 int8) holds
+    picks of a row with itself, adding and subtracting: the pairs among {A, B, new row} of k_cs_apply with A == B"""
+    from upd_diet_cases import self_pairs
+
     o = Oracle('port')
     bad = []
-    for seed, shape in ((1, (10, 12)), (2, (7, 5)), (3, (4, 300))):
-        k = int_matrix(seed, *shape, -16, 16)
+    for seed, shape, lim in ((1, (10, 12), 16), (2, (7, 5), 16), (3, (4, 300), 16), (0, (12, 10), 128)):
+        k = int_matrix(seed, *shape, -lim, lim)
         p, st = hip.solve_sharded(k, **SINGLE)
-        if p != o.solve(k, **SINGLE) or st['sharded_chains'] < 1:
+        want = o.solve(k, **SINGLE)
+        if p != want or st['sharded_chains'] < 1:
             bad.append(seed)
+    add, sub = self_pairs(want)
+    assert add >= 1 and sub >= 1  # the last case does hold picks of a row with itself, of either sign
     out(bad=bad)
 
 

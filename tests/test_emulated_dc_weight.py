@@ -1,9 +1,10 @@
 """The tunable latency-penalty weight of the -dc / -pdc selectors (_binary.solve_each, da_solve_batch_opts, da4ml_amd.cmvm.solve_tradeoff) with the
 product's kernels on the emulated device of tests/test_emulated_device.py, through tests/emu/dc_weight_worker.py.
 
-A weight changes the rank of a table entry and nothing else.  Four sites form ranks (table_insert, table_update, and in k_iter_update the
-side-by-side re-evaluation and the block creation): one of them left on the method's constant still gives valid adder graphs, but which pick
-wins then depends on where a block lies in the table and on which path wrote it last.  So every case and weight is compared with the records of
+A weight changes the rank of a table entry and nothing else.  Ranks are formed in one place, the block evaluator of cmvm_engine.hip, which four
+paths write blocks through (table_insert, table_update, and in k_iter_update the side-by-side re-evaluation and the block creation): a path left
+on the method's constant would still give valid adder graphs, but which pick wins would depend on where a block lies in the table and on which
+path wrote it last.  So every case and weight is compared with the records of
 tests/golden/dc_weight_golden.json -- a patched copy of the restatement, tests/golden/make_dc_weight_golden.py --, the ends of the weight axis
 with the unpatched restatement, and the narrow chains must not move when the table's geometry does."""
 

@@ -27,6 +27,8 @@ O = Oracle("ref" if os.path.exists(os.path.join(os.environ["DA_ROOT"], "oracle",
 cases = [(int_matrix(0, 16, 16, -128, 128), {}), (int_matrix(1, 48, 40, -128, 128), dict(method0="wmc", method1="wmc", decompose_dc=-1, search_all_decompose_dc=False)),
          (int_matrix(2, 9, 20, -8, 8), dict(adder_size=1, carry_size=-1)), (int_matrix(3, 33, 7, -64, 64), dict(hard_dc=1))]
 cases += [random_case(s)[:2] for s in (1003, 1006, 1012, 1021, 1030, 1033)]
+# 12x10 int8 as one wmc chain: picks of a row with itself, adding and subtracting (the pairs among {A, B, new row} of k_cs_apply with A == B)
+cases += [(int_matrix(0, 12, 10, -128, 128), dict(method0="wmc", method1="wmc", decompose_dc=-1, search_all_decompose_dc=False))]
 same, chains = [], 0
 for k, kw in cases:
     p, st = hip.solve_sharded(k, rank=0, world=1, **kw)
@@ -80,7 +82,7 @@ def test_sharded_phases_single_process():
     r = subprocess.run([sys.executable, '-c', SINGLE], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
-    assert all(out['same']) and len(out['same']) == 10, out
+    assert all(out['same']) and len(out['same']) == 11, out
     assert out['chains'] >= 10
 
 
