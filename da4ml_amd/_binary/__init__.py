@@ -28,7 +28,8 @@ _i32p = np.ctypeslib.ndpointer(np.int32, flags='C_CONTIGUOUS')
 EXPORTS = (
     'da_last_error da_last_error_code da_version da_device_count da_set_device da_get_lsb_loc da_iceil_log2 da_cost_add da_int_arr_to_csd '
     'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_batch_seeded da_solve_batch_opts da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
-    'da_result_stats da_free da_timings da_engine_stats da_dais_run da_dais_last_error da_dais_run_on'
+    'da_result_stats da_free da_timings da_engine_stats da_dais_run da_dais_last_error da_dais_run_on '
+    'da_dais_compile da_dais_exec_info da_dais_exec_scratch da_dais_exec_run da_dais_exec_free'
 ).split()
 
 
@@ -549,10 +550,177 @@ def dais_interp_run(bin_logic, data, n_threads: int = 1, executor: str = 'host')
     return out
 
 
+_DAIS_RESIDENT = 3  # DA_DAIS_DEVICE_RESIDENT
+_DAIS_TYPES = {np.dtype(np.float64): 0, np.dtype(np.float32): 1}  # DA_DAIS_F64 / DA_DAIS_F32
+
+
+def _is_torch_tensor(x) -> bool:
+    return type(x).__module__.split('.')[0] == 'torch' and hasattr(x, 'data_ptr')  # (no import of torch for the asking)
+
+
+def _np_rows(a: np.ndarray, width: int):
+    """row stride in elements of a 2-d array whose rows are contiguous, None when it has to be copied first"""
+    if a.shape[0] == 0:
+        return width
+    if width > 1 and a.strides[1] != a.itemsize:
+        return None
+    if a.shape[0] == 1:
+        return width
+    if a.strides[0] % a.itemsize or a.strides[0] < width * a.itemsize:
+        return None
+    return a.strides[0] // a.itemsize
+
+
+class DaisExecutable:
+    """One DAIS program, or a chain of them, compiled once and run many times (``da_dais_compile``, include/da4ml_hip.h; no reference
+    counterpart).  ``ex(x)`` is bit for bit ``for p in programs: x = dais_interp_run(p, x)``: the outputs of a stage are the raw inputs
+    of the next one, which its input statements quantise and wrap -- whatever the values are.
+
+    ``x``: a numpy array ``[n, n_in]`` of float32 / float64 (anything else is converted to float64) gives a numpy array (float64 unless
+    ``out_dtype`` says float32), on the executor asked for: ``'device'`` (kernel ``k_dais_exec``; the samples are staged in tiles),
+    ``'host'`` or ``'host-scalar'`` (both without a GPU).  A torch tensor on a HIP device, float32 / float64, rows contiguous in their last
+    dimension and any row stride, gives a torch tensor on that device: the kernel reads and writes the tensors in place through
+    ``data_ptr()``, queued on ``torch.cuda.current_stream()`` with no synchronisation (on torch's default stream, which has no handle to
+    queue on, the call waits for the stream and for its own run instead; a chain with lookup tables always waits, to report a lookup out of
+    bounds).  ``out``: an array / tensor ``[n, n_out]`` to write into (a slice of a wider one will do).  One handle's resident runs belong on
+    one stream at a time: they share the handle's scratch memory."""
+
+    def __init__(self, programs):
+        progs = [np.ascontiguousarray(np.ravel(p), dtype=np.int32) for p in programs]
+        L = lib()
+        L.da_dais_compile.restype = C.c_void_p
+        L.da_dais_compile.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        L.da_dais_exec_info.argtypes = [C.c_void_p, _i64p]
+        L.da_dais_exec_scratch.argtypes = [C.c_void_p, _i64p]
+        L.da_dais_exec_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        L.da_dais_exec_free.argtypes = [C.c_void_p]
+        L.da_dais_last_error.restype = C.c_char_p
+        self._h = None
+        ptrs = (C.c_void_p * max(len(progs), 1))(*[p.ctypes.data for p in progs])
+        sizes = np.array([p.size for p in progs], np.int64)
+        h = L.da_dais_compile(len(progs), ptrs, sizes.ctypes.data)
+        if not h:
+            raise RuntimeError(L.da_dais_last_error().decode())
+        self._h = h
+        i = np.zeros(8, np.int64)
+        L.da_dais_exec_info(h, i)
+        self.n_stages, self.n_in, self.n_out = int(i[0]), int(i[1]), int(i[2])
+        self._static = dict(n_stages=int(i[0]), n_in=int(i[1]), n_out=int(i[2]), n_ops=int(i[3]), n_slots=int(i[4]),
+                            regfile='hbm' if i[5] == 0 else str(int(i[5])), regfile_bytes_per_sample=int(i[6]), has_tables=bool(i[7]))  # fmt: skip
+
+    @property
+    def info(self) -> dict:
+        """what ``da_dais_exec_info`` and ``da_dais_exec_scratch`` report: sizes, slot count, register-file variant; address and bytes of
+        the register-file scratch on the device and the device allocations runs have made so far"""
+        s = np.zeros(3, np.int64)
+        lib().da_dais_exec_scratch(self._handle(), s)
+        return dict(self._static, scratch_ptr=int(s[0]), scratch_bytes=int(s[1]), allocations=int(s[2]))
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError('this DaisExecutable is closed')
+        return self._h
+
+    def close(self):
+        h, self._h = getattr(self, '_h', None), None
+        if h and _lib is not None:
+            _lib.da_dais_exec_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _run(self, where, xp, xt, xs, n, yp, yt, ys, n_threads, stream):
+        L = lib()
+        if L.da_dais_exec_run(self._handle(), xp, xt, xs, n, yp, yt, ys, int(n_threads), where, stream) != 0:
+            raise RuntimeError(L.da_dais_last_error().decode())
+
+    def __call__(self, x, out=None, out_dtype=None, executor: str = 'device', n_threads: int = 0):
+        if _is_torch_tensor(x):
+            return self._call_torch(x, out, out_dtype, executor)
+        if executor not in _DAIS_EXECUTORS:
+            raise ValueError(f'unknown DAIS executor {executor!r} (one of {sorted(_DAIS_EXECUTORS)})')
+        x = np.asarray(x)
+        if x.dtype not in _DAIS_TYPES:
+            x = x.astype(np.float64)
+        if x.ndim != 2:
+            assert self.n_in > 0 and x.size % self.n_in == 0, f'Input size {x.size} is not divisible by {self.n_in}'
+            x = x.reshape(-1, self.n_in)
+        if x.shape[1] != self.n_in:
+            raise ValueError(f'input has {x.shape[1]} columns, the executable {self.n_in} inputs')
+        xs = _np_rows(x, self.n_in)
+        if xs is None:
+            x = np.ascontiguousarray(x)
+            xs = self.n_in
+        n = x.shape[0]
+        if out is None:
+            out = np.zeros((n, self.n_out), np.dtype(out_dtype or np.float64))
+        if not isinstance(out, np.ndarray) or out.dtype not in _DAIS_TYPES or out.shape != (n, self.n_out) or (out_dtype is not None and np.dtype(out_dtype) != out.dtype):
+            raise ValueError(f'out must be a float32 / float64 numpy array of shape {(n, self.n_out)}' + (f' and dtype {np.dtype(out_dtype)}' if out_dtype is not None else ''))
+        ys = _np_rows(out, self.n_out)
+        if ys is None or not out.flags.writeable:
+            raise ValueError('out must be writeable with rows that are contiguous in the last dimension')
+        self._run(_DAIS_EXECUTORS[executor], x.ctypes.data, _DAIS_TYPES[x.dtype], xs, n, out.ctypes.data, _DAIS_TYPES[out.dtype], ys, n_threads, None)
+        return out
+
+    def _call_torch(self, x, out, out_dtype, executor):
+        import torch
+
+        types = {torch.float64: 0, torch.float32: 1}
+        if executor not in ('device', 'gpu'):
+            raise ValueError("a tensor on the device runs with executor='device'")
+        if not x.is_cuda or x.dtype not in types or x.dim() != 2 or x.shape[1] != self.n_in:
+            raise ValueError(f'x must be a float32 / float64 tensor of shape [n, {self.n_in}] on a HIP device')
+
+        def rows(t, width):
+            if t.shape[0] == 0:
+                return width
+            if width > 1 and t.stride(1) != 1:
+                return None
+            if t.shape[0] == 1:
+                return width
+            return t.stride(0) if t.stride(0) >= width else None
+
+        xs = rows(x, self.n_in)
+        if xs is None:
+            raise ValueError('the rows of x must be contiguous in the last dimension (any row stride >= n_in)')
+        n = x.shape[0]
+        if out is None:
+            out = torch.empty((n, self.n_out), dtype=out_dtype or torch.float64, device=x.device)
+        if not _is_torch_tensor(out) or out.device != x.device or out.dtype not in types or tuple(out.shape) != (n, self.n_out) or (out_dtype is not None and out_dtype != out.dtype):
+            raise ValueError(f'out must be a float32 / float64 tensor of shape {(n, self.n_out)} on {x.device}')
+        ys = rows(out, self.n_out)
+        if ys is None:
+            raise ValueError('the rows of out must be contiguous in the last dimension (any row stride >= n_out)')
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream()
+            if not stream.cuda_stream:  # torch's default stream is the null stream: nothing to queue on
+                stream.synchronize()
+            self._run(_DAIS_RESIDENT, x.data_ptr(), types[x.dtype], xs, n, out.data_ptr(), types[out.dtype], ys, 0, stream.cuda_stream or None)
+        return out
+
+
+def dais_compile(programs) -> DaisExecutable:
+    """Compile one DAIS program (an int32 array, ``CombLogic.to_binary()``) or a sequence of them -- the stages of a ``Pipeline``, each
+    feeding the next -- into a ``DaisExecutable``.  Raises with the reference's messages for an invalid program, and
+    ``stage s has n outputs, stage s+1 expects m inputs`` for stages that do not fit."""
+    if isinstance(programs, np.ndarray) and programs.ndim == 1:
+        programs = [programs]
+    return DaisExecutable(programs)
+
+
 # the reference exposes the raw extension module as `da4ml._binary.cmvm_bin` (imported by trace/fixed_variable.py:15)
 cmvm_bin = SimpleNamespace(
     solve=solve, kernel_decompose=kernel_decompose, csd_decompose=csd_decompose, int_arr_to_csd=int_arr_to_csd,
     get_lsb_loc=get_lsb_loc, iceil_log2=iceil_log2, cost_add=cost_add,
 )  # fmt: skip
 
-__all__ = ['dais_interp_run', 'int_arr_to_csd', 'csd_decompose', 'get_lsb_loc', 'kernel_decompose', 'solve', 'iceil_log2', 'solve_many', 'cost_add']
+__all__ = ['dais_interp_run', 'dais_compile', 'DaisExecutable','int_arr_to_csd', 'csd_decompose', 'get_lsb_loc', 'kernel_decompose', 'solve', 'iceil_log2', 'solve_many', 'cost_add']

@@ -88,6 +88,9 @@ DAIS_HD int64_t eval(const Step &s, int64_t a, int64_t b, int64_t c, double x) {
     }
 }
 
+// an output of a program from the value of its result op; in a compiled chain (dais_exec.h) also the raw input of the next stage
+DAIS_HD double out_value(int64_t v, int neg, double scale) { return (double)(neg ? -v : v) * scale; }
+
 // which operand registers a step reads: bit 0 a, bit 1 b, bit 2 c
 DAIS_HD int reads(int32_t kind) {
     switch (kind) {

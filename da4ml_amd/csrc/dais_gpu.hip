@@ -12,12 +12,17 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "../../include/da4ml_hip.h"
+
 #include "dais_core.h"
+#include "dais_exec.h"
 
 namespace {
 
@@ -205,5 +210,290 @@ void dais_run_gpu(const dais::Program &g, const double *inputs, int64_t n_sample
         const int64_t idx = (int64_t)(int32_t)(uint32_t)(fault & 0xFFFFFFFFull);
         throw std::runtime_error("Logic lookup index out of bounds: index=" + std::to_string(idx) +
                                  ", table_size=" + std::to_string((fault >> 32) & 0x7FFFFFFFull));
+    }
+}
+
+// ================================================================================================================================
+// Compiled executables (da_dais_compile, include/da4ml_hip.h): a chain of programs as ONE statement list over one register file,
+// uploaded once; k_dais_exec runs all stages of a sample in one thread and one launch.
+// ================================================================================================================================
+
+dais::Chain dais::build_chain(const std::vector<Program> &stages) {
+    const int S = (int)stages.size();
+    if (S < 1) throw std::runtime_error("a DAIS executable needs at least one program");
+    for (int s = 0; s + 1 < S; ++s)
+        if (stages[s].n_out != stages[s + 1].n_in)
+            throw std::runtime_error("stage " + std::to_string(s) + " has " + std::to_string(stages[s].n_out) + " outputs, stage " + std::to_string(s + 1) +
+                                     " expects " + std::to_string(stages[s + 1].n_in) + " inputs");
+    Chain c;
+    c.n_stages = S, c.n_in = stages[0].n_in, c.n_out = stages[S - 1].n_out;
+    std::vector<int64_t> base((size_t)S + 1, 0);  // value numbers of the chain: base[s] + statement index in stage s
+    for (int s = 0; s < S; ++s) base[s + 1] = base[s] + stages[s].n_ops;
+    const int64_t total = base[S];
+    c.steps.resize((size_t)total);
+    std::vector<std::array<int64_t, 3>> opnd((size_t)total);  // the values a statement reads (a boundary input: the producer's value in [0])
+    std::vector<int64_t> last((size_t)total, -1);             // last reader of a value
+    for (int s = 0; s < S; ++s) {
+        const Program &g = stages[s];
+        std::vector<int32_t> off;
+        for (const auto &t : g.tables) {
+            off.push_back((int32_t)c.tables.size());
+            c.tables.insert(c.tables.end(), t.begin(), t.end());
+        }
+        c.has_tables |= !g.tables.empty();
+        for (int64_t i = 0; i < g.n_ops; ++i) {
+            const int64_t v = base[s] + i;
+            ChainStep d{};
+            d.s = g.steps[i], d.src = SRC_EXTERNAL;
+            const int rd = reads(d.s.kind);
+            opnd[v] = {(rd & 1) ? base[s] + d.s.a : -1, (rd & 2) ? base[s] + d.s.b : -1, (rd & 4) ? base[s] + d.s.c : -1};
+            if (d.s.kind == K_INPUT && s > 0) {
+                const Program &p = stages[s - 1];
+                const int32_t o = p.out_idx[d.s.a];
+                if (o < 0)
+                    d.src = SRC_ABSENT;
+                else
+                    opnd[v][0] = base[s - 1] + o, d.src = 0, d.src_neg = p.out_neg[d.s.a], d.src_scale = p.out_scale[d.s.a];
+            }
+            if (d.s.kind == K_LUT) d.tab_off = off[d.s.aux], d.tab_len = (int32_t)g.tables[d.s.aux].size();
+            for (int64_t r : opnd[v])
+                if (r >= 0) last[r] = v;
+            c.steps[v] = d;
+        }
+    }
+    for (int32_t o : stages[S - 1].out_idx)
+        if (o >= 0) last[base[S - 1] + o] = total;  // read by the output stage
+    // an inner stage's output that the next stage never reads keeps its slot to the end of its own stage all the same
+    std::vector<char> pinned((size_t)total, 0);
+    for (int s = 0; s + 1 < S; ++s)
+        for (int32_t o : stages[s].out_idx)
+            if (o >= 0 && last[base[s] + o] < base[s + 1]) pinned[base[s] + o] = 1;
+
+    std::vector<int32_t> slot_of((size_t)total, -1), free_slots;
+    int64_t n_slots = 0;
+    for (int s = 0; s < S; ++s) {
+        if (s > 0)
+            for (int32_t o : stages[s - 1].out_idx)
+                if (o >= 0 && pinned[base[s - 1] + o]) free_slots.push_back(slot_of[base[s - 1] + o]), pinned[base[s - 1] + o] = 0;
+        for (int64_t v = base[s]; v < base[s + 1]; ++v) {
+            ChainStep &d = c.steps[v];
+            const std::array<int64_t, 3> &r = opnd[v];
+            if (r[0] >= 0) (d.s.kind == K_INPUT ? d.src : d.s.a) = slot_of[r[0]];
+            if (r[1] >= 0) d.s.b = slot_of[r[1]];
+            if (r[2] >= 0) d.s.c = slot_of[r[2]];
+            for (int k = 0; k < 3; ++k) {  // operands whose last reader is this statement release their slot (once per value)
+                if (r[k] < 0 || last[r[k]] != v || pinned[r[k]]) continue;
+                bool dup = false;
+                for (int m = 0; m < k; ++m) dup |= r[m] == r[k];
+                if (!dup) free_slots.push_back(slot_of[r[k]]);
+            }
+            int32_t slot;
+            if (!free_slots.empty()) {
+                slot = free_slots.back();
+                free_slots.pop_back();
+            } else
+                slot = (int32_t)n_slots++;
+            slot_of[v] = d.dst = slot;
+            if (last[v] < 0 && !pinned[v]) free_slots.push_back(slot);  // never read: the slot is free again right away
+        }
+    }
+    c.n_slots = std::max<int64_t>(n_slots, 1);
+    const Program &e = stages[S - 1];
+    c.outs.resize((size_t)e.n_out);
+    for (int64_t j = 0; j < e.n_out; ++j) c.outs[j] = ChainOut{e.out_idx[j] < 0 ? -1 : slot_of[base[S - 1] + e.out_idx[j]], e.out_neg[j], e.out_scale[j]};
+    return c;
+}
+
+namespace {
+
+// One thread per sample, all stages of the chain.  x: [n][x_stride] of In, y: [n][y_stride] of Out (strides in elements).
+// Register file [slot][sample] in HBM at regs, `pitch` samples per slot (the tile): the 64 lanes of a wavefront touch 512 consecutive
+// bytes per access.  (A register file in the block's LDS was built and left out: DESIGN.md section 9.)
+template <class In, class Out>
+__global__ __launch_bounds__(TPB) void k_dais_exec(const dais::ChainStep *__restrict__ steps, int64_t n_steps, const dais::ChainOut *__restrict__ outs,
+                                                   int64_t n_out, const int32_t *__restrict__ tables, const In *__restrict__ x, int64_t x_stride,
+                                                   Out *__restrict__ y, int64_t y_stride, int64_t *__restrict__ regs, int64_t pitch, int64_t n,
+                                                   unsigned long long *__restrict__ lut_fault) {
+    const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (t >= n) return;
+    int64_t *R = regs + t;
+    const int64_t P = pitch;
+    const In *xs = x + t * x_stride;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        const dais::ChainStep &d = steps[i];  // uniform address: scalar loads
+        const dais::Step &s = d.s;
+        const int rd = dais::reads(s.kind);
+        const int64_t a = (rd & 1) ? R[(int64_t)s.a * P] : 0;
+        const int64_t b = (rd & 2) ? R[(int64_t)s.b * P] : 0;
+        const int64_t c = (rd & 4) ? R[(int64_t)s.c * P] : 0;
+        int64_t v;
+        if (s.kind == dais::K_LUT) {
+            const int64_t idx = dais::lut_index(s, a);
+            if (idx < 0 || idx >= d.tab_len) {
+                // record the first offending index and keep going with 0; the host turns it into the reference's error
+                atomicCAS(lut_fault, 0ull, (1ull << 63) | ((unsigned long long)(uint32_t)d.tab_len << 32) | (unsigned long long)(uint32_t)idx);
+                v = 0;
+            } else
+                v = tables[d.tab_off + idx];
+        } else {
+            double xin = 0.0;  // K_INPUT: an input of the chain, or the producing stage's output straight from the register file
+            if (s.kind == dais::K_INPUT) {
+                if (d.src == dais::SRC_EXTERNAL)
+                    xin = (double)xs[s.a];
+                else if (d.src >= 0)
+                    xin = dais::out_value(R[(int64_t)d.src * P], d.src_neg, d.src_scale);
+            }
+            v = dais::eval(s, a, b, c, xin);
+        }
+        R[(int64_t)d.dst * P] = v;
+    }
+    Out *ys = y + t * y_stride;
+    for (int64_t j = 0; j < n_out; ++j) {
+        const dais::ChainOut o = outs[j];
+        ys[j] = o.slot < 0 ? (Out)0.0 : (Out)dais::out_value(R[(int64_t)o.slot * P], o.neg, o.scale);
+    }
+}
+
+// grow-only device allocation owned by a handle
+struct Scratch {
+    void *p = nullptr;
+    size_t bytes = 0;
+    // true when it had to allocate
+    bool need(size_t want) {
+        if (want <= bytes) return false;
+        if (p) DAIS_HIP(hipFree(p));
+        p = nullptr, bytes = 0;
+        DAIS_HIP(hipMalloc(&p, want));
+        bytes = want;
+        return true;
+    }
+    ~Scratch() { (void)hipFree(p); }
+};
+
+size_t elem_size(int type) { return type == DA_DAIS_F32 ? sizeof(float) : sizeof(double); }
+
+}  // namespace
+
+struct DaisDevExec {
+    dais::ChainStep *steps = nullptr;
+    dais::ChainOut *outs = nullptr;
+    int32_t *tables = nullptr;
+    unsigned long long *fault = nullptr;
+    hipStream_t stream = nullptr;
+    int64_t tile_cap = 0;  // samples per launch the memory of the device allows (fixed at creation)
+    Scratch regs, x, y;
+    int64_t allocations = 0;
+};
+
+void dais_dev_free(DaisDevExec *d) {
+    if (!d) return;
+    (void)hipFree(d->steps), (void)hipFree(d->outs), (void)hipFree(d->tables), (void)hipFree(d->fault);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;
+}
+
+namespace {
+
+template <class In, class Out> void launch_exec(DaisDevExec *d, const dais::Chain &c, hipStream_t st, const void *x, int64_t x_stride, void *y, int64_t y_stride,
+                                                int64_t pitch, int64_t n) {
+    hipLaunchKernelGGL((k_dais_exec<In, Out>), dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, st, d->steps, (int64_t)c.steps.size(), d->outs, c.n_out,
+                       d->tables, (const In *)x, x_stride, (Out *)y, y_stride, (int64_t *)d->regs.p, pitch, n, d->fault);
+    DAIS_HIP(hipGetLastError());
+}
+
+void launch_typed(DaisDevExec *d, const dais::Chain &c, hipStream_t st, const void *x, int in_type, int64_t x_stride, void *y, int out_type, int64_t y_stride,
+                  int64_t pitch, int64_t n) {
+    if (in_type == DA_DAIS_F32)
+        out_type == DA_DAIS_F32 ? launch_exec<float, float>(d, c, st, x, x_stride, y, y_stride, pitch, n)
+                                : launch_exec<float, double>(d, c, st, x, x_stride, y, y_stride, pitch, n);
+    else
+        out_type == DA_DAIS_F32 ? launch_exec<double, float>(d, c, st, x, x_stride, y, y_stride, pitch, n)
+                                : launch_exec<double, double>(d, c, st, x, x_stride, y, y_stride, pitch, n);
+}
+
+}  // namespace
+
+DaisDevExec *dais_dev_create(const dais::Chain &c) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return nullptr;
+    DaisDevExec *d = new DaisDevExec;
+    try {
+        auto upload = [&](auto **dst, const auto &v) {
+            using T = typename std::remove_reference<decltype(v)>::type::value_type;
+            DAIS_HIP(hipMalloc((void **)dst, std::max<size_t>(v.size(), 1) * sizeof(T)));
+            if (!v.empty()) DAIS_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        };
+        upload(&d->steps, c.steps);
+        upload(&d->outs, c.outs);
+        upload(&d->tables, c.tables);
+        DAIS_HIP(hipMalloc((void **)&d->fault, sizeof(unsigned long long)));
+        DAIS_HIP(hipMemset(d->fault, 0, sizeof(unsigned long long)));
+        DAIS_HIP(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+        // tile: as many samples as fit a register-file budget (1/4 of free memory, at most 2^22 samples), as dais_run_gpu
+        size_t free_b = 0, total_b = 0;
+        DAIS_HIP(hipMemGetInfo(&free_b, &total_b));
+        const int64_t per_sample = c.n_slots * 8 + (c.n_in + c.n_out) * 8;
+        d->tile_cap = std::min<int64_t>((int64_t)1 << 22, std::max<int64_t>((int64_t)(free_b / 4) / std::max<int64_t>(per_sample, 1), TPB));
+    } catch (...) {
+        dais_dev_free(d);
+        throw;
+    }
+    return d;
+}
+
+void dais_dev_scratch(const DaisDevExec *d, int64_t *s3) {
+    s3[0] = d ? (int64_t)(intptr_t)d->regs.p : 0, s3[1] = d ? (int64_t)d->regs.bytes : 0, s3[2] = d ? d->allocations : 0;
+}
+
+void dais_dev_run(DaisDevExec *d, const dais::Chain &c, const void *in, int in_type, int64_t in_stride, int64_t n_samples, void *out, int out_type,
+                  int64_t out_stride, bool resident, void *stream) {
+    if (!d) throw std::runtime_error("no HIP device: the DAIS device executor needs a GPU (the host executor does not)");
+    if (n_samples <= 0) return;
+    int64_t tile = std::min(n_samples, d->tile_cap);
+    if (const char *e = std::getenv("DA4ML_DAIS_TILE"))  // experiment knob: samples per launch (cache residency vs occupancy)
+        tile = std::max<int64_t>(1, std::min<int64_t>(tile, std::atoll(e)));
+    tile = (tile + TPB - 1) / TPB * TPB;
+    hipStream_t st = stream ? (hipStream_t)stream : d->stream;
+    d->allocations += d->regs.need((size_t)(c.n_slots * tile) * sizeof(int64_t));
+    const size_t in_sz = elem_size(in_type), out_sz = elem_size(out_type);
+    // a tile of host rows is staged as one span of its rows with their stride
+    auto span = [](int64_t rows, int64_t stride, int64_t row) { return (size_t)((rows - 1) * stride + row); };
+    if (!resident) {
+        d->allocations += d->x.need(std::max<size_t>(span(tile, in_stride, c.n_in) * in_sz, 1));
+        d->allocations += d->y.need(std::max<size_t>(span(tile, out_stride, c.n_out) * out_sz, 1));
+    }
+    for (int64_t s0 = 0; s0 < n_samples; s0 += tile) {
+        const int64_t n = std::min(tile, n_samples - s0);
+        const char *xi = (const char *)in + (size_t)(s0 * in_stride) * in_sz;
+        char *yo = (char *)out + (size_t)(s0 * out_stride) * out_sz;
+        if (resident) {
+            launch_typed(d, c, st, xi, in_type, in_stride, yo, out_type, out_stride, tile, n);
+            continue;
+        }
+        if (c.n_in > 0) DAIS_HIP(hipMemcpyAsync(d->x.p, xi, span(n, in_stride, c.n_in) * in_sz, hipMemcpyHostToDevice, st));
+        launch_typed(d, c, st, d->x.p, in_type, in_stride, d->y.p, out_type, out_stride, tile, n);
+        if (c.n_out > 0) {
+            if (out_stride == c.n_out)
+                DAIS_HIP(hipMemcpyAsync(yo, d->y.p, (size_t)(n * c.n_out) * out_sz, hipMemcpyDeviceToHost, st));
+            else  // the elements between the rows of the caller's array are not the executor's to write
+                for (int64_t r = 0; r < n; ++r)
+                    DAIS_HIP(hipMemcpyAsync(yo + (size_t)(r * out_stride) * out_sz, (const char *)d->y.p + (size_t)(r * out_stride) * out_sz,
+                                            (size_t)c.n_out * out_sz, hipMemcpyDeviceToHost, st));
+        }
+    }
+    // queued work of a caller's stream stays queued; a chain with table statements, the handle's own stream and staged runs are waited for
+    if (!resident || !stream || c.has_tables) {
+        unsigned long long fault = 0;
+        if (c.has_tables) {
+            DAIS_HIP(hipMemcpyAsync(&fault, d->fault, sizeof fault, hipMemcpyDeviceToHost, st));
+            DAIS_HIP(hipStreamSynchronize(st));
+            if (fault) DAIS_HIP(hipMemset(d->fault, 0, sizeof fault));  // the handle stays usable
+        } else
+            DAIS_HIP(hipStreamSynchronize(st));
+        if (fault) {
+            const int64_t idx = (int64_t)(int32_t)(uint32_t)(fault & 0xFFFFFFFFull);
+            throw std::runtime_error("Logic lookup index out of bounds: index=" + std::to_string(idx) +
+                                     ", table_size=" + std::to_string((fault >> 32) & 0x7FFFFFFFull));
+        }
     }
 }

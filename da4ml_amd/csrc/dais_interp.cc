@@ -10,10 +10,12 @@
 // step at load time, invalid programs are rejected at load time -- and a sample is then a single pass over that array
 // with one int64 register file.
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <exception>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -23,6 +25,7 @@
 #include "../../include/da4ml_hip.h"
 
 #include "dais_core.h"
+#include "dais_exec.h"
 
 namespace dais {
 namespace {
@@ -290,6 +293,69 @@ void run_scalar(const Program &g, const SlotProgram &sp, const double *x, double
     }
 }
 
+// Runs work(lo, hi) over [0, n_samples) on host threads, split like the reference (bindings.cc:57-66): at least 32 samples per
+// thread; n_threads <= 0 = all host threads.  The first exception of a worker is rethrown.
+template <class F> void parallel_samples(int64_t n_samples, int n_threads, F &&body) {
+    int64_t hw = (int64_t)std::max(1u, std::thread::hardware_concurrency());
+    int64_t want = n_threads <= 0 ? hw : std::min<int64_t>(n_threads, hw);
+    int64_t per = std::max<int64_t>(n_samples / std::max<int64_t>(want, 1), 32);
+    int64_t n_thr = (n_samples + per - 1) / per;
+    std::exception_ptr err;
+    std::mutex mu;
+    auto work = [&](int64_t lo, int64_t hi) {
+        try {
+            body(lo, hi);
+        } catch (...) {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!err) err = std::current_exception();
+        }
+    };
+    if (n_thr <= 1)
+        work(0, n_samples);
+    else {
+        std::vector<std::thread> th;
+        for (int64_t t = 0; t < n_thr; ++t) th.emplace_back(work, t * per, std::min(n_samples, (t + 1) * per));
+        for (auto &t : th) t.join();
+    }
+    if (err) std::rethrow_exception(err);
+}
+
+// One sample through a compiled chain (dais_exec.h): the per-thread code of k_dais_exec, statement for statement
+void run_chain_scalar(const Chain &c, const double *x, double *y, int64_t *reg) {
+    for (const ChainStep &d : c.steps) {
+        const Step &s = d.s;
+        const int rd = reads(s.kind);
+        const int64_t a = (rd & 1) ? reg[s.a] : 0, b = (rd & 2) ? reg[s.b] : 0, cc = (rd & 4) ? reg[s.c] : 0;
+        if (s.kind == K_LUT) {
+            const int64_t idx = lut_index(s, a);
+            if (idx < 0 || idx >= d.tab_len)
+                bad("Logic lookup index out of bounds: index=" + std::to_string(idx) + ", table_size=" + std::to_string(d.tab_len));
+            reg[d.dst] = c.tables[(size_t)(d.tab_off + idx)];
+            continue;
+        }
+        double xin = 0.0;
+        if (s.kind == K_INPUT) {
+            if (d.src == SRC_EXTERNAL)
+                xin = x[s.a];
+            else if (d.src >= 0)
+                xin = out_value(reg[d.src], d.src_neg, d.src_scale);
+        }
+        reg[d.dst] = eval(s, a, b, cc, xin);
+    }
+    for (size_t j = 0; j < c.outs.size(); ++j) {
+        const ChainOut &o = c.outs[j];
+        y[j] = o.slot < 0 ? 0.0 : out_value(reg[o.slot], o.neg, o.scale);
+    }
+}
+
+inline double load_elem(const void *p, int type, int64_t i) { return type == DA_DAIS_F32 ? (double)((const float *)p)[i] : ((const double *)p)[i]; }
+inline void store_elem(void *p, int type, int64_t i, double v) {
+    if (type == DA_DAIS_F32)
+        ((float *)p)[i] = (float)v;
+    else
+        ((double *)p)[i] = v;
+}
+
 thread_local std::string g_dais_err;
 
 }  // namespace
@@ -321,41 +387,130 @@ int da_dais_run_on(const int32_t *program, int64_t n_words, const double *inputs
         SlotProgram sp;
         if (where == DA_DAIS_HOST_SCALAR) sp.n_slots = dais_assign_slots(g, sp.steps, sp.dst, sp.slot_of);
         if (where != DA_DAIS_HOST && where != DA_DAIS_HOST_SCALAR) bad("da_dais_run_on: unknown executor " + std::to_string(where));
-        // split like the reference (bindings.cc:57-66): at least 32 samples per thread
-        int64_t hw = (int64_t)std::max(1u, std::thread::hardware_concurrency());
-        int64_t want = n_threads <= 0 ? hw : std::min<int64_t>(n_threads, hw);
-        int64_t per = std::max<int64_t>(n_samples / std::max<int64_t>(want, 1), 32);
-        int64_t n_thr = (n_samples + per - 1) / per;
-        std::exception_ptr err;
-        std::mutex mu;
-        auto work = [&](int64_t lo, int64_t hi) {
-            try {
-                std::vector<int64_t> reg((size_t)std::max<int64_t>(g.n_ops, 1) * BLOCK, 0);
-                if (where == DA_DAIS_HOST_SCALAR) {
-                    std::vector<int64_t> slots((size_t)sp.n_slots, 0);
-                    for (int64_t s = lo; s < hi; ++s) run_scalar(g, sp, inputs + s * g.n_in, outputs + s * g.n_out, slots.data());
-                    return;
-                }
-                for (int64_t s = lo; s < hi; s += BLOCK)
-                    run_block(g, inputs + s * g.n_in, outputs + s * g.n_out, (int)std::min<int64_t>(BLOCK, hi - s), reg.data());
-            } catch (...) {
-                std::lock_guard<std::mutex> lk(mu);
-                if (!err) err = std::current_exception();
+        parallel_samples(n_samples, n_threads, [&](int64_t lo, int64_t hi) {
+            std::vector<int64_t> reg((size_t)std::max<int64_t>(g.n_ops, 1) * BLOCK, 0);
+            if (where == DA_DAIS_HOST_SCALAR) {
+                std::vector<int64_t> slots((size_t)sp.n_slots, 0);
+                for (int64_t s = lo; s < hi; ++s) run_scalar(g, sp, inputs + s * g.n_in, outputs + s * g.n_out, slots.data());
+                return;
             }
-        };
-        if (n_thr <= 1)
-            work(0, n_samples);
-        else {
-            std::vector<std::thread> th;
-            for (int64_t t = 0; t < n_thr; ++t) th.emplace_back(work, t * per, std::min(n_samples, (t + 1) * per));
-            for (auto &t : th) t.join();
-        }
-        if (err) std::rethrow_exception(err);
+            for (int64_t s = lo; s < hi; s += BLOCK)
+                run_block(g, inputs + s * g.n_in, outputs + s * g.n_out, (int)std::min<int64_t>(BLOCK, hi - s), reg.data());
+        });
         return DA_OK;
     } catch (const std::exception &e) {
         g_dais_err = e.what();
         return DA_ERR_RUNTIME;
     }
 }
+
+}  // extern "C"
+
+// ---- compiled executables: decode, validate and slot-assign once, run many times (include/da4ml_hip.h) ------------------------
+struct da_dais_exec {
+    std::vector<Program> stages;
+    Chain chain;
+    DaisDevExec *dev = nullptr;  // null without a device: only the two device modes fail then
+    std::mutex mu;               // runs of one handle are serialised
+    int64_t widest = 1, most_ops = 1;
+    ~da_dais_exec() { dais_dev_free(dev); }
+};
+
+namespace {
+
+// HOST: the block executor stage by stage on blocks of BLOCK samples; HOST_SCALAR: the device's per-value path over the chain's slots
+void exec_run_host(const da_dais_exec &h, const void *in, int in_type, int64_t in_stride, int64_t n_samples, void *out, int out_type, int64_t out_stride,
+                   int n_threads, bool scalar) {
+    const Chain &c = h.chain;
+    parallel_samples(n_samples, n_threads, [&](int64_t lo, int64_t hi) {
+        std::vector<double> xa((size_t)(h.widest * BLOCK), 0.0), xb((size_t)(h.widest * BLOCK), 0.0);
+        if (scalar) {
+            std::vector<int64_t> slots((size_t)c.n_slots, 0);
+            for (int64_t s = lo; s < hi; ++s) {
+                for (int64_t j = 0; j < c.n_in; ++j) xa[j] = load_elem(in, in_type, s * in_stride + j);
+                run_chain_scalar(c, xa.data(), xb.data(), slots.data());
+                for (int64_t j = 0; j < c.n_out; ++j) store_elem(out, out_type, s * out_stride + j, xb[j]);
+            }
+            return;
+        }
+        std::vector<int64_t> reg((size_t)(h.most_ops * BLOCK), 0);
+        for (int64_t s = lo; s < hi; s += BLOCK) {
+            const int nb = (int)std::min<int64_t>(BLOCK, hi - s);
+            for (int k = 0; k < nb; ++k)
+                for (int64_t j = 0; j < c.n_in; ++j) xa[k * c.n_in + j] = load_elem(in, in_type, (s + k) * in_stride + j);
+            double *x = xa.data(), *y = xb.data();
+            for (const Program &g : h.stages) {
+                run_block(g, x, y, nb, reg.data());
+                std::swap(x, y);
+            }
+            for (int k = 0; k < nb; ++k)  // (x: the last stage's outputs after the swap)
+                for (int64_t j = 0; j < c.n_out; ++j) store_elem(out, out_type, (s + k) * out_stride + j, x[k * c.n_out + j]);
+        }
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+da_dais_exec *da_dais_compile(int n_stages, const int32_t *const *programs, const int64_t *n_words) {
+    try {
+        if (n_stages < 1 || !programs || !n_words) bad("da_dais_compile: at least one program is needed");
+        std::unique_ptr<da_dais_exec> h(new da_dais_exec);
+        for (int s = 0; s < n_stages; ++s) {
+            if (!programs[s] || n_words[s] < 4) bad("Invalid binary logic data");
+            h->stages.push_back(decode(programs[s], n_words[s]));
+            h->widest = std::max({h->widest, h->stages.back().n_in, h->stages.back().n_out});
+            h->most_ops = std::max(h->most_ops, h->stages.back().n_ops);
+        }
+        h->chain = build_chain(h->stages);
+        h->dev = dais_dev_create(h->chain);
+        return h.release();
+    } catch (const std::exception &e) {
+        g_dais_err = e.what();
+        return nullptr;
+    }
+}
+
+int da_dais_exec_info(const da_dais_exec *h, int64_t *info8) {
+    if (!h || !info8) return DA_ERR_RUNTIME;
+    info8[0] = h->chain.n_stages, info8[1] = h->chain.n_in, info8[2] = h->chain.n_out, info8[3] = (int64_t)h->chain.steps.size();
+    info8[4] = h->chain.n_slots, info8[5] = 0, info8[6] = h->chain.n_slots * 8, info8[7] = h->chain.has_tables;
+    return DA_OK;
+}
+
+int da_dais_exec_scratch(const da_dais_exec *h, int64_t *scratch3) {
+    if (!h || !scratch3) return DA_ERR_RUNTIME;
+    dais_dev_scratch(h->dev, scratch3);
+    return DA_OK;
+}
+
+int da_dais_exec_run(da_dais_exec *h, const void *in, int in_type, int64_t in_row_stride, int64_t n_samples, void *out, int out_type,
+                     int64_t out_row_stride, int n_threads, int where, void *stream) {
+    try {
+        if (!h) bad("da_dais_exec_run: no executable");
+        const Chain &c = h->chain;
+        if ((in_type != DA_DAIS_F64 && in_type != DA_DAIS_F32) || (out_type != DA_DAIS_F64 && out_type != DA_DAIS_F32))
+            bad("da_dais_exec_run: element types are DA_DAIS_F64 or DA_DAIS_F32");
+        if (in_row_stride < c.n_in || out_row_stride < c.n_out)
+            bad("da_dais_exec_run: row strides (" + std::to_string(in_row_stride) + ", " + std::to_string(out_row_stride) + ") are smaller than the rows (" +
+                std::to_string(c.n_in) + ", " + std::to_string(c.n_out) + ")");
+        if (where != DA_DAIS_HOST && where != DA_DAIS_HOST_SCALAR && where != DA_DAIS_DEVICE && where != DA_DAIS_DEVICE_RESIDENT)
+            bad("da_dais_exec_run: unknown executor " + std::to_string(where));
+        if (n_samples <= 0) return DA_OK;
+        if ((!in && c.n_in > 0) || (!out && c.n_out > 0)) bad("da_dais_exec_run: null sample pointer");
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (where == DA_DAIS_DEVICE || where == DA_DAIS_DEVICE_RESIDENT)
+            dais_dev_run(h->dev, c, in, in_type, in_row_stride, n_samples, out, out_type, out_row_stride, where == DA_DAIS_DEVICE_RESIDENT, stream);
+        else
+            exec_run_host(*h, in, in_type, in_row_stride, n_samples, out, out_type, out_row_stride, n_threads, where == DA_DAIS_HOST_SCALAR);
+        return DA_OK;
+    } catch (const std::exception &e) {
+        g_dais_err = e.what();
+        return DA_ERR_RUNTIME;
+    }
+}
+
+void da_dais_exec_free(da_dais_exec *h) { delete h; }
 
 }  // extern "C"

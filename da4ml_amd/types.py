@@ -212,6 +212,27 @@ def minimal_kif(qi: QInterval, symmetric: bool = False) -> Precision:
     return Precision(qi.min < 0, int(ceil(log2(mag))) - frac, frac)
 
 
+def _kif_columns(ff: np.ndarray):
+    """``minimal_kif`` of every row of ``ff[:, :3]`` = (min, max, step) at once: int64 ``[n, 3]``, or ``None`` where the columns hold
+    something whose result could differ from the scalar function's (a step that is no power of two, non-finite bounds).  The logarithms
+    are read off the binary exponents (``frexp``), which is exact where ``log2`` of the scalar function is."""
+    lo_f, hi_f, st = (np.asarray(ff[:, j], dtype=np.float64) for j in range(3))
+    zero = (lo_f == hi_f) & (lo_f == 0)
+    with np.errstate(all='ignore'):
+        m, e = np.frexp(st)
+        lo, hi = np.rint(lo_f / st), np.rint(hi_f / st)  # (round half to even, as round())
+        mag = np.maximum(np.abs(lo), hi + 1)
+        mm, me = np.frexp(mag)
+    ok = zero | ((m == 0.5) & np.isfinite(mag) & (mag >= 1) & (mag < 2.0**45))
+    if not np.all(ok):
+        return None
+    frac = 1 - e.astype(np.int64)
+    ints = np.where(mm == 0.5, me - 1, me).astype(np.int64) - frac
+    out = np.stack([(lo_f < 0).astype(np.int64), ints, frac], axis=1)
+    out[zero] = 0
+    return out
+
+
 class _Encoder(json.JSONEncoder):
     def default(self, o):
         if hasattr(o, 'to_dict'):
@@ -503,6 +524,33 @@ class CombLogic(NamedTuple):
     def save_binary(self, path: str | Path, version: int = 0):
         self.to_binary(version).tofile(str(path))
 
+    def program_words(self, version: int = 0) -> np.ndarray:
+        """The words of ``to_binary()``.  For a solver result whose statements are still the C ABI's arrays (a lazy ``OpList``) they are
+        built from the columns of those arrays, without an ``Op`` object per statement; anything else goes through ``to_binary``."""
+        ops = self.ops
+        if not (isinstance(ops, OpList) and ops._lazy()) or self.lookup_tables is not None:
+            return self.to_binary(version)
+        kifs = _kif_columns(ops._ff)
+        if kifs is None or np.any(ops._ci[:, 2] == 8):
+            return self.to_binary(version)
+        n_in, n_out = self.shape
+        head = np.concatenate([[1, version, n_in, n_out, len(ops), 0], self.inp_shifts, self.out_idxs, self.out_shifts, self.out_negs]).astype(np.int32)
+        code = np.zeros((len(ops), 8), dtype=np.int32)
+        code[:, 0] = ops._ci[:, 2]
+        code[:, 1:3] = ops._ci[:, 0:2]
+        data = ops._ci[:, 3].astype(np.int64).view(np.uint64)
+        code[:, 3] = (data & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32)  # the low word first, as the uint64 view of to_binary
+        code[:, 4] = (data >> np.uint64(32)).astype(np.uint32).view(np.int32)
+        code[:, 5:8] = kifs
+        return np.concatenate([head, code.ravel()])
+
+    def compile(self):
+        """This graph as a compile-once / run-many executable of the native library (``da4ml_amd._binary.DaisExecutable``): the program is
+        built, decoded and slot-assigned once, and ``ex(x)`` runs it on numpy arrays or on torch tensors that live on the GPU."""
+        from ._binary import dais_compile
+
+        return dais_compile([self.program_words()])
+
     def predict(self, data, n_threads: int = 0, executor: str = 'host'):
         """Integer-exact batch execution through the DAIS binary program, like the reference (``types.py:549-581``);
         ``executor='device'`` runs the samples on the GPU (one thread per sample) instead of on host threads."""
@@ -525,6 +573,30 @@ class Pipeline(NamedTuple):
         for sol in self.solutions:
             out = sol(out, quantize=quantize, debug=debug)
         return out
+
+    def compile(self):
+        """All stages as ONE executable of the native library (``da4ml_amd._binary.DaisExecutable``): on the device a sample runs through
+        every stage in one kernel launch, the values at a stage boundary staying in the register file.
+
+        The result is that of ``predict`` of one stage after the other: the outputs of a stage (shifted and negated as it declares) are
+        handed to the input statements of the next, which wrap them into the intervals that stage declares.  The register stages of
+        ``to_pipeline`` are exact under this rule: their inner boundaries have shift 0, no negation and the producer's interval.  ``solve``
+        declares the input intervals of its second stage from the first stage's result ops BEFORE their output shift and sign (as the
+        reference does, ``api.cc:103-115``): where the first stage shifts or negates an output, a value can wrap at the boundary -- in
+        this executable exactly as in the stage-by-stage composition on the host, which it reproduces bit for bit, not "fixes"."""
+        from ._binary import dais_compile
+
+        return dais_compile([s.program_words() for s in self.solutions])
+
+    def predict(self, data, n_threads: int = 0, executor: str = 'host'):
+        """Integer-exact batch execution of all stages (``compile()`` and one run; see there for what happens at a stage boundary).
+        ``executor`` as for ``CombLogic.predict``; ``data`` may also be a torch tensor on the GPU with ``executor='device'``."""
+        if isinstance(data, (list, tuple)):
+            data = np.concatenate([np.asarray(a).reshape(len(a), -1) for a in data], axis=-1)
+        if n_threads <= 0:
+            n_threads = int(os.environ.get('DA_DEFAULT_THREADS', 0))
+        with self.compile() as ex:
+            return ex(data, executor=executor, n_threads=n_threads)
 
     @property
     def kernel(self):

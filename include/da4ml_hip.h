@@ -196,6 +196,46 @@ const char *da_dais_last_error(void);
 int da_dais_run_on(const int32_t *program, int64_t n_words, const double *inputs, int64_t n_samples, double *outputs, int n_threads,
                    int where);
 
+/* ---- compiled DAIS executables: compile once, run many times ------------------------------------------------------ */
+/* A handle for one DAIS program or a chain of `n_stages` of them (n_out of program s = n_in of program s+1); no reference
+ * counterpart.  The result of a run is bit for bit that of running the programs one after the other with da_dais_run: the outputs
+ * of stage s, (double)(neg ? -v : v) * out_scale and 0.0 for an absent output, are the raw inputs of stage s+1, quantised and
+ * wrapped by its input statements -- for any input, in range or not (csrc/dais_core.h computes every value on every path).
+ * da_dais_compile decodes and validates every program (the reference's messages; "stage s has n outputs, stage s+1 expects m
+ * inputs"), assigns register slots once over the WHOLE chain -- an input statement of stage s+1 reads the value behind the
+ * producing stage's output, so the register file is as large as the largest live set of the chain -- and, with a device present,
+ * uploads statements, outputs and tables to the current device.  Without a device it compiles all the same; only the two device
+ * modes of a run fail then.  Returns NULL on error (message: da_dais_last_error, calling thread). */
+typedef struct da_dais_exec da_dais_exec;
+da_dais_exec *da_dais_compile(int n_stages, const int32_t *const *programs, const int64_t *n_words);
+/* info8 = stages, n_in, n_out, statements in total, slots, register-file variant chosen (0: HBM, the only one), register-file
+ * bytes per sample, has table statements */
+int da_dais_exec_info(const da_dais_exec *h, int64_t *info8);
+/* scratch3 = address of the handle's register-file scratch on the device (0: none yet), its bytes, device
+ * allocations made by runs so far: a steady run allocates nothing */
+int da_dais_exec_scratch(const da_dais_exec *h, int64_t *scratch3);
+/* Runs `n_samples` rows.  in / out: element type DA_DAIS_F64 or DA_DAIS_F32 (float inputs are widened exactly, float outputs are
+ * the exact double rounded once), row strides in elements (>= n_in / n_out; the elements of a row are contiguous; elements
+ * between the rows of `out` are left alone).  `where`:
+ *   DA_DAIS_HOST, DA_DAIS_HOST_SCALAR  host pointers; the host block executor stage by stage / the device's per-value path over
+ *                            the compiled chain and its slots (test aid, as for da_dais_run_on); `n_threads` as da_dais_run;
+ *   DA_DAIS_DEVICE           host pointers, staged tile by tile through the handle's buffers; returns when the results are there;
+ *   DA_DAIS_DEVICE_RESIDENT  device pointers of the current device (the one of da_dais_compile), used in place.  Everything is
+ *                            queued on `stream` (a hipStream_t) and the call returns without waiting -- except that with
+ *                            stream == NULL the handle's own stream is used and waited for, and that a chain with table
+ *                            statements is waited for to turn the kernel's fault word into "Logic lookup index out of bounds".
+ * Kernel k_dais_exec (csrc/dais_gpu.hip): one thread per sample, all stages in one launch per tile, nothing of an inner stage
+ * goes to memory as a double.  Register file [slot][sample] in HBM: scratch of the handle, allocated at the first run, grown
+ * only for a larger tile; tiles capped as for da_dais_run_on, DA4ML_DAIS_TILE honoured.
+ * Runs of one handle are serialised by a mutex of the handle and share its scratch: hand one handle's resident runs to one
+ * stream at a time.  Different handles are independent.  Returns DA_OK or DA_ERR_RUNTIME (da_dais_last_error). */
+#define DA_DAIS_F64 0
+#define DA_DAIS_F32 1
+#define DA_DAIS_DEVICE_RESIDENT 3
+int da_dais_exec_run(da_dais_exec *h, const void *in, int in_type, int64_t in_row_stride, int64_t n_samples, void *out, int out_type,
+                     int64_t out_row_stride, int n_threads, int where, void *stream);
+void da_dais_exec_free(da_dais_exec *h);
+
 /* ---- instrumentation for the benchmark harness ------------------------------------------------------------- */
 /* t[31] = chains summed over the sampled launches; t[30] = capacity retries; t[18..29] = shader-clock cycles per kernel phase (7 of k_iter_select, 5 of k_iter_update);
  * t[0..17] = loop_ms (HIP events around the greedy-loop launches), dist_ms, total_ms, lockstep iterations,
