@@ -333,6 +333,7 @@ def solve_many(
     search_all_decompose_dc: bool = True,
     _stats: bool = False,
     seeds=None,
+    tie_order='random',
 ):
     """Solve independent matrices concurrently on the GPU (addition to the reference API; same options as ``solve``).
 
@@ -342,11 +343,24 @@ def solve_many(
     (``da_solve_batch_seeded``, include/da4ml_hip.h): a problem with a seed other than 0 settles equally scored pairs of its greedy
     chains by the order that seed gives instead of the reference's -- a random restart of the search; the same seed gives the same
     result in every batch.  ``da4ml_amd.cmvm.solve_restarts`` is the user-facing entry.
+
+    ``tie_order``: which order a seed other than 0 gives -- ``'random'`` (the default) or ``'newest'`` (``DA_TIE_NEWEST``: the pair
+    with the newest row still wins a tie, as in the reference; the seed orders what lies below), one name for the whole batch.
+    Seed 0 is the reference's result under either.
     """
+    order = tie_order_code(tie_order)
     ks = [_kernel(k) for k in kernels]
     n = len(ks)
     if n == 0:
         return []
+    if order != TIE_ORDERS['random']:  # (da_solve_batch_seeded stays the random order: the other goes through the per-problem structs)
+        if seeds is None:
+            seeds = [0] * n
+        if len(seeds) != n:
+            raise ValueError('seeds must hold one entry per kernel')
+        shared = dict(method0=method0, method1=method1, hard_dc=hard_dc, decompose_dc=decompose_dc, adder_size=adder_size, carry_size=carry_size,
+                      search_all_decompose_dc=search_all_decompose_dc, tie_order=tie_order)  # fmt: skip
+        return solve_each(ks, [dict(shared, seed=s) for s in seeds], qintervals=qintervals, latencies=latencies, _stats=_stats)
     seed_arr = None
     if seeds is not None:
         if len(seeds) != n:
@@ -379,6 +393,14 @@ def solve_many(
 
 
 DC_WEIGHT_DEFAULT = -1.0  # DA_DC_WEIGHT_DEFAULT: the reference's constant per method
+TIE_ORDERS = {'random': 0, 'newest': 1}  # DA_TIE_RANDOM, DA_TIE_NEWEST
+
+
+def tie_order_code(name) -> int:
+    """``DA_TIE_*`` of a tie order's name; anything else is a ``ValueError``"""
+    if not isinstance(name, str) or name not in TIE_ORDERS:
+        raise ValueError(f'tie order must be one of {sorted(TIE_ORDERS)}, not {name!r}')
+    return TIE_ORDERS[name]
 
 
 class SolveOpts(C.Structure):
@@ -395,10 +417,11 @@ class SolveOpts(C.Structure):
         ('search_all_decompose_dc', C.c_int),
         ('dc_weight', C.c_float),
         ('seed', C.c_uint64),
+        ('tie_order', C.c_uint32),
     ]
 
 
-_EACH_DEFAULTS = dict(method0='wmc', method1='auto', hard_dc=-1, decompose_dc=-2, adder_size=-1, carry_size=-1, search_all_decompose_dc=True, seed=0, dc_weight=None)
+_EACH_DEFAULTS = dict(method0='wmc', method1='auto', hard_dc=-1, decompose_dc=-2, adder_size=-1, carry_size=-1, search_all_decompose_dc=True, seed=0, dc_weight=None, tie_order='random')
 
 
 def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool = False):
@@ -406,7 +429,8 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
 
     ``options``: one dict per kernel of ``solve``'s keywords (``method0``, ``method1``, ``hard_dc``, ``decompose_dc``, ``adder_size``,
     ``carry_size``, ``search_all_decompose_dc``) plus ``seed`` (tie seed, 0: the reference's order) and ``dc_weight`` (latency-penalty
-    weight of the ``*-dc`` / ``*-pdc`` selectors: a finite number >= 0, or ``None``: the reference's constant per method).  Missing keys
+    weight of the ``*-dc`` / ``*-pdc`` selectors: a finite number >= 0, or ``None``: the reference's constant per method) and ``tie_order``
+    (``'random'`` or ``'newest'``: the order a seed other than 0 gives, see ``solve_many``; anything else is a ``ValueError``).  Missing keys
     have ``solve``'s defaults.  ``qintervals`` / ``latencies`` as for ``solve_many``.  The result of a problem depends on nothing but its
     own matrix and options.  ``da4ml_amd.cmvm.solve_tradeoff`` is the user-facing entry for weight sweeps."""
     ks = [_kernel(k) for k in kernels]
@@ -427,7 +451,7 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
         if o['dc_weight'] is not None and not (0.0 <= w < float('inf')):  # (a negative number is not a way to spell "unset" here)
             raise ValueError('dc_weight must be a finite number >= 0')
         opts[i] = SolveOpts(C.sizeof(SolveOpts), o['method0'].encode(), o['method1'].encode(), int(o['hard_dc']), int(o['decompose_dc']), int(o['adder_size']),
-                            int(o['carry_size']), int(bool(o['search_all_decompose_dc'])), w, int(o['seed']) & 0xFFFFFFFFFFFFFFFF)  # fmt: skip
+                            int(o['carry_size']), int(bool(o['search_all_decompose_dc'])), w, int(o['seed']) & 0xFFFFFFFFFFFFFFFF, tie_order_code(o['tie_order']))  # fmt: skip
     n_in = np.array([k.shape[0] for k in ks], np.int64)
     n_out = np.array([k.shape[1] for k in ks], np.int64)
     kptr = (C.c_void_p * n)(*[k.ctypes.data for k in ks])

@@ -5,7 +5,7 @@ from typing import NamedTuple, TypedDict
 
 import numpy as np
 
-from .._binary import kernel_decompose, solve, solve_each, solve_many
+from .._binary import kernel_decompose, solve, solve_each, solve_many, tie_order_code
 from ..types import CombLogic, Op, QInterval
 
 
@@ -48,7 +48,7 @@ def first_strict_minimum(costs) -> int:
     return best
 
 
-def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = False, **solve_options):
+def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = False, order: str = 'random', **solve_options):
     """Best of ``n_restarts`` greedy searches of one matrix (addition to the reference API; ``solve_options`` as for ``solve``).
 
     Most greedy steps have several equally scored pairs, and the reference takes the last of them in its sorted table.
@@ -58,10 +58,19 @@ def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = Fa
     accumulates it (float32, op order: ``multi_gpu.pipeline_cost_f32``), so a tie returns restart 0 and the returned cost is
     never above ``solve``'s.  The same ``seed`` gives the same restarts on every run.
 
+    ``order``: how a restart's seed orders tied pairs.  ``'random'`` (the default): which pair wins is random.  ``'newest'``: the pair
+    with the newest row still wins, as in the reference -- that is what makes the reference's order a good one --, and the seed orders
+    only what lies below (the older row of the pair, then shift and sign).  Restart 0 is ``solve`` itself under either; the seeds are the
+    same.  At 64x64 and above no random restart beats ``solve`` while most newest-first restarts do (README).  Anything else is a
+    ``ValueError``.
+
     ``return_all=True``: ``(best_index, [Pipeline, ...], [cost, ...])`` instead of the winning Pipeline."""
     from ..multi_gpu import pipeline_cost_f32
 
+    tie_order_code(order)
     seeds = restart_seeds(n_restarts, seed)
+    if order != 'random':
+        solve_options = {**solve_options, 'tie_order': order}
     per_kernel = {k: [v] * len(seeds) for k, v in solve_options.items() if k in ('qintervals', 'latencies') and v is not None}
     opts = {k: v for k, v in solve_options.items() if k not in ('qintervals', 'latencies')}
     pipes = solve_many([kernel] * len(seeds), seeds=seeds, **opts, **per_kernel)

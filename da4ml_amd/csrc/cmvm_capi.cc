@@ -184,8 +184,15 @@ int da_solve_batch_opts(int count, const float *const *kernels, const int64_t *n
         std::vector<da::Problem> probs((size_t)count);
         for (int i = 0; i < count; ++i) {
             da::Problem &p = probs[i];
-            const da_solve_opts &o = opts[i];
-            if (o.struct_size != sizeof(da_solve_opts)) throw std::invalid_argument("opts[" + std::to_string(i) + "].struct_size is not sizeof(da_solve_opts)");
+            // A caller built against the struct without tie_order passes an array of THAT struct: elements lie struct_size bytes apart, and
+            // its problems run the random order.  (struct_size is the first field of both.)
+            const uint32_t stride = opts[0].struct_size;
+            if (stride != sizeof(da_solve_opts) && stride != DA_SOLVE_OPTS_SIZE_V1) throw std::invalid_argument("opts[0].struct_size is not sizeof(da_solve_opts)");
+            da_solve_opts o{};
+            std::memcpy(&o, reinterpret_cast<const unsigned char *>(opts) + (size_t)i * stride, stride);
+            if (o.struct_size != stride) throw std::invalid_argument("opts[" + std::to_string(i) + "].struct_size is not sizeof(da_solve_opts)");
+            const uint32_t tie_order = stride == sizeof(da_solve_opts) ? o.tie_order : (uint32_t)DA_TIE_RANDOM;
+            if (tie_order != DA_TIE_RANDOM && tie_order != DA_TIE_NEWEST) throw std::invalid_argument("tie_order must be DA_TIE_RANDOM or DA_TIE_NEWEST");
             if (!o.method0 || !o.method1) throw std::invalid_argument("opts[" + std::to_string(i) + "]: method0 and method1 must be strings");
             if (o.dc_weight != DA_DC_WEIGHT_DEFAULT && !(o.dc_weight >= 0.0f && o.dc_weight <= std::numeric_limits<float>::max()))
                 throw std::invalid_argument("dc_weight must be a finite number >= 0");
@@ -207,6 +214,7 @@ int da_solve_batch_opts(int count, const float *const *kernels, const int64_t *n
             p.opt.carry_size = o.carry_size;
             p.opt.search_all = o.search_all_decompose_dc != 0;
             p.opt.seed = o.seed;
+            p.opt.tie_order = o.seed ? tie_order : da::TIE_ORDER_RANDOM;  // (seed 0 is the reference whatever the order says: one problem to the de-duplication)
             p.opt.dc_weight = o.dc_weight == DA_DC_WEIGHT_DEFAULT ? -1.0f : o.dc_weight + 0.0f;  // (+ 0: -0 and 0 are one weight)
         }
         std::vector<da::ChainStats> stats;
@@ -228,7 +236,7 @@ int da_solve_batch_seeded(int count, const float *const *kernels, const int64_t 
     std::vector<da_solve_opts> opts;
     try {  // (an allocation failure must not cross the C ABI)
         opts.assign((size_t)std::max(count, 0), da_solve_opts{(uint32_t)sizeof(da_solve_opts), method0, method1, hard_dc, decompose_dc, adder_size, carry_size,
-                                                              search_all_decompose_dc, DA_DC_WEIGHT_DEFAULT, 0});
+                                                              search_all_decompose_dc, DA_DC_WEIGHT_DEFAULT, 0, DA_TIE_RANDOM});
         for (int i = 0; i < count; ++i) opts[i].seed = seeds ? seeds[i] : 0;
     } catch (const std::exception &e) {
         return fail(e);

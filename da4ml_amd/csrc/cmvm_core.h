@@ -358,6 +358,69 @@ DA_HD void tie_word_rows(uint64_t tie, uint64_t seed, uint32_t &id0, uint32_t &i
 }
 DA_HD int tie_word_idx(uint64_t tie, uint64_t seed) { return (int)(((uint32_t)tie & 0x7Fu) ^ tie_k7(seed)); }
 
+// ------------------------------------------------------------------------------------ the second seeded order: newest row first
+// The reference lets the larger (id1, id0) win a tie: the pair that re-uses the newest row.  The random order above throws that away; this
+// one keeps it and moves only what lies below: among equal ranks the larger id1 still wins, pairs of one id1 are ordered by a keyed
+// 24-bit bijection of id0, keys of one pair by idx ^ k7 as above (so the within-block order, tie_block_pos, is shared by both orders):
+//   word = id1 << 31 | mix24(id0) << 7 | (idx ^ k7)                                         below 2^55, injective as the others
+//   mix24: xor with the seed's low 24 bits, multiply by TIE_MUL mod 2^24, xor-shift by 12 (its own inverse on 24 bits), xor with the
+//          seed's bits 24 .. 47.
+// A bound word (rank << 32 | word >> 23) holds id1 and the top eight bits of the mixed id0: coarser than (rank, word), as before.
+// No reference counterpart: with seed 0 the order is the reference's, whatever TIE_ORDER_* says.
+constexpr uint32_t TIE_ORDER_RANDOM = 0, TIE_ORDER_NEWEST = 1, TIE_ORDER_COUNT = 2;
+constexpr uint32_t TIE_ID_MASK = 0xFFFFFFu;
+static_assert((((TIE_MUL & TIE_ID_MASK) * (TIE_MUL_INV & TIE_ID_MASK)) & TIE_ID_MASK) == 1, "inverse of the tie multiplier mod 2^24");
+constexpr uint32_t tie_xs12(uint32_t h) { return h ^ (h >> 12); }
+static_assert(tie_xs12(tie_xs12(0xABCDEFu)) == 0xABCDEFu && tie_xs12(tie_xs12(0xFFFFFFu)) == 0xFFFFFFu && tie_xs12(tie_xs12(0x800001u)) == 0x800001u,
+              "the 12-bit xor-shift is its own inverse on 24 bits");
+DA_HD uint32_t tie_mix24(uint32_t id0, uint64_t seed) {
+    uint32_t h = id0 ^ ((uint32_t)seed & TIE_ID_MASK);
+    h = (h * (uint32_t)(TIE_MUL & TIE_ID_MASK)) & TIE_ID_MASK;
+    h ^= h >> 12;
+    return h ^ ((uint32_t)(seed >> 24) & TIE_ID_MASK);
+}
+DA_HD uint32_t tie_unmix24(uint32_t h, uint64_t seed) {
+    h ^= (uint32_t)(seed >> 24) & TIE_ID_MASK;
+    h ^= h >> 12;
+    h = (h * (uint32_t)(TIE_MUL_INV & TIE_ID_MASK)) & TIE_ID_MASK;
+    return h ^ ((uint32_t)seed & TIE_ID_MASK);
+}
+DA_HD uint64_t tie_word_newest(uint32_t id0, uint32_t id1, int idx, uint64_t seed) {
+    return ((uint64_t)id1 << 31) | ((uint64_t)tie_mix24(id0, seed) << 7) | (uint64_t)tie_block_pos((uint32_t)idx, seed);
+}
+// Both seeded orders as ONE expression of the 48 bits (id1 << 24 | id0), for code that learns the order at run time (the SEEDED kernels of the
+// engine): the random order mixes all 48 bits (mask 2^48 - 1, xor-shift 24, the seed's bits 16 .. 63 on top), the newest-first order the low 24
+// (mask 2^24 - 1, xor-shift 12, the seed's bits 24 .. 47) and passes id1 through.
+DA_HD uint64_t tie_pair_mix(uint64_t pair, uint64_t seed, uint32_t order) {
+    const uint64_t m = order == TIE_ORDER_NEWEST ? (uint64_t)TIE_ID_MASK : TIE_PAIR_MASK;
+    const int s = order == TIE_ORDER_NEWEST ? 12 : 24;
+    uint64_t h = ((pair ^ seed) * TIE_MUL) & m;
+    h ^= h >> s;
+    h ^= (order == TIE_ORDER_NEWEST ? seed >> 24 : seed >> 16) & m;
+    return (pair & ~m) | h;
+}
+DA_HD uint64_t tie_pair_unmix(uint64_t w, uint64_t seed, uint32_t order) {
+    const uint64_t m = order == TIE_ORDER_NEWEST ? (uint64_t)TIE_ID_MASK : TIE_PAIR_MASK;
+    const int s = order == TIE_ORDER_NEWEST ? 12 : 24;
+    uint64_t h = (w ^ (order == TIE_ORDER_NEWEST ? seed >> 24 : seed >> 16)) & m;
+    h ^= h >> s;
+    h = ((h * TIE_MUL_INV) ^ seed) & m;
+    return (w & ~m) | h;
+}
+// seed != 0 wanted, as tie_word_seeded
+DA_HD uint64_t tie_word_seeded(uint32_t id0, uint32_t id1, int idx, uint64_t seed, uint32_t order) {
+    return (tie_pair_mix(((uint64_t)id1 << 24) | (uint64_t)id0, seed, order) << 7) | (uint64_t)tie_block_pos((uint32_t)idx, seed);
+}
+// any seed, either order (seed 0: the reference's word under both)
+DA_HD uint64_t tie_word(uint32_t id0, uint32_t id1, int idx, uint64_t seed, uint32_t order) {
+    return seed ? tie_word_seeded(id0, id1, idx, seed, order) : tie_word(id0, id1, idx);
+}
+DA_HD void tie_word_rows(uint64_t tie, uint64_t seed, uint32_t order, uint32_t &id0, uint32_t &id1) {
+    const uint64_t h = seed ? tie_pair_unmix(tie >> 7, seed, order) : tie >> 7;
+    id0 = (uint32_t)(h & TIE_ID_MASK);
+    id1 = (uint32_t)(h >> 24);
+}
+
 // ------------------------------------------------------------------------------------ qint / latency
 // qint_add(q0, q1, shift, false, sub) (state_opr.cc:8-29); all operations exact or single-rounded IEEE
 DA_HD void qint_add_pair(const RowInfo &a, const RowInfo &b, int shift, int sub, float &lo, float &hi, float &step) {

@@ -379,6 +379,7 @@ struct ChainDev {
                                       // the SEEDED instantiations of the kernels only (last field: the offsets the others use are what they were)
     float dc_weight;                  // latency-penalty weight of the -dc / -pdc methods (entry_rank, cmvm_core.h); the host always fills it, by default with the method's
                                       // constant.  Read by the WEIGHTED instantiations only: the others keep the constant as a literal (last field, as tie_seed was)
+    uint32_t tie_order;               // which seeded tie order a chain with tie_seed != 0 runs (TIE_ORDER_*, cmvm_core.h).  Read by the SEEDED instantiations only (last field again)
 };
 
 __constant__ Log2Table c_log2;
@@ -485,17 +486,21 @@ struct Ctx {
 
 // ---- tie order of a chain.  SEEDED is a template parameter of every kernel that forms, compares or takes apart a tie word, as MANYCOL is of the
 // selection kernel: the unseeded instantiations are instruction for instruction what they were, a seeded chain pays one 48-bit multiply per word.
+// A seeded chain runs one of two orders (TIE_ORDER_*, cmvm_core.h): `order`, uniform per chain, read from the descriptor by the SEEDED instantiations
+// only and held beside the chain context -- by the block evaluator in the kernels that write blocks, in a scalar of its own in the selection --, not
+// in it: the unseeded kernels are built from the same Ctx and carry none of it.  Both orders are one expression (tie_pair_mix with an order); the
+// within-block order (blk_pos) is the same for both.
 // Every site goes through these three (the code that writes blocks: through the block evaluator below, which is built on them): a tie word
 // formed one way and compared with one formed the other gives picks that are valid adder graphs but not the maximum of the chain's order.
-template <bool SEEDED> __device__ __forceinline__ unsigned long long tie_of(uint32_t id0, uint32_t id1, int idx, unsigned long long seed) {
+template <bool SEEDED> __device__ __forceinline__ unsigned long long tie_of(uint32_t id0, uint32_t id1, int idx, unsigned long long seed, uint32_t order) {
     if constexpr (SEEDED)
-        return tie_word_seeded(id0, id1, idx, seed);
+        return tie_word_seeded(id0, id1, idx, seed, order);
     else
         return tie_word(id0, id1, idx);
 }
-template <bool SEEDED> __device__ __forceinline__ void tie_rows(unsigned long long tie, unsigned long long seed, uint32_t &id0, uint32_t &id1) {
+template <bool SEEDED> __device__ __forceinline__ void tie_rows(unsigned long long tie, unsigned long long seed, uint32_t order, uint32_t &id0, uint32_t &id1) {
     unsigned long long h = tie >> 7;
-    if constexpr (SEEDED) h = tie_pair_unmix(h, seed);
+    if constexpr (SEEDED) h = tie_pair_unmix(h, seed, order);
     id0 = (uint32_t)(h & 0xFFFFFFu);
     id1 = (uint32_t)(h >> 24);
 }
@@ -525,6 +530,7 @@ template <bool WEIGHTED> __device__ __forceinline__ uint32_t rank_of(const Ctx &
 template <bool SEEDED, bool WEIGHTED> struct BlockEval {
     const Ctx &c;
     uint32_t dcw;  // bits of the chain's latency-penalty weight in the WEIGHTED instantiations, unused (0) in the others
+    uint32_t ord;  // the chain's seeded tie order (TIE_ORDER_*) in the SEEDED instantiations, unused (0) in the others
     // candidate word of key `k` with count `n` in a block of rows with overlap `ov`, latency difference `dl`: rank << 8 | position in the
     // within-block order, 0 = not selectable
     __device__ __forceinline__ unsigned long long candidate(uint32_t n, uint32_t k, int ov, float dl) const {
@@ -536,7 +542,7 @@ template <bool SEEDED, bool WEIGHTED> struct BlockEval {
     static __device__ __forceinline__ uint32_t rank_of_best(unsigned long long best) { return (uint32_t)(best >> 8); }
     __device__ __forceinline__ uint32_t idx_of_best(unsigned long long best) const { return blk_pos<SEEDED>((uint32_t)(best & 0xFF), c.seed); }
     // tie word and bound word (0: nothing selectable) of the best entry (rank, idx) of the block of rows lo <= hi
-    __device__ __forceinline__ unsigned long long tie(uint32_t lo, uint32_t hi, uint32_t idx) const { return tie_of<SEEDED>(lo, hi, (int)idx, c.seed); }
+    __device__ __forceinline__ unsigned long long tie(uint32_t lo, uint32_t hi, uint32_t idx) const { return tie_of<SEEDED>(lo, hi, (int)idx, c.seed, ord); }
     __device__ __forceinline__ unsigned long long word(uint32_t lo, uint32_t hi, uint32_t rank, uint32_t idx) const {
         return rank ? bound_word(rank, tie(lo, hi, idx)) : 0ull;
     }
@@ -961,7 +967,7 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __global__ voi
         if (lane_id() == 0) g->unknown_hit = 1;
         return;
     }
-    table_insert(BlockEval<SEEDED, WEIGHTED>{c, WEIGHTED ? f2u(g->dc_weight) : 0u}, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; });
+    table_insert(BlockEval<SEEDED, WEIGHTED>{c, WEIGHTED ? f2u(g->dc_weight) : 0u, SEEDED ? g->tie_order : 0u}, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; });
 }
 
 // ================================================================================= k_iter_select2: the next pick, one step ahead
@@ -1012,7 +1018,7 @@ constexpr int QL_CAP = DA_CAND_CAP * 4;  // entries touching the pick's rows the
 // written.  For the substitution block of a step whose pick is not known ahead (the first step of a chain; an overflowed candidate list): 4 bytes per
 // slot twice (8 + 8 MB for a 256x256 chain, once per chain).  rank 0: nothing selectable.  red_*: one LDS word per wave.  Ends with a block barrier.
 template <bool SEEDED = false>
-__device__ __forceinline__ void table_argmax_block(ChainDev *g, unsigned long long seed, uint32_t &rank, unsigned long long &tie, uint32_t *red_rank, unsigned long long *red_tie) {
+__device__ __forceinline__ void table_argmax_block(ChainDev *g, unsigned long long seed, uint32_t order, uint32_t &rank, unsigned long long &tie, uint32_t *red_rank, unsigned long long *red_tie) {
     const DA_GLOBAL uint32_t *hrank = (const DA_GLOBAL uint32_t *)g->hrank;
     const DA_GLOBAL unsigned long long *hkey = (const DA_GLOBAL unsigned long long *)g->hkey;
     const uint32_t C = g->C;
@@ -1039,7 +1045,7 @@ __device__ __forceinline__ void table_argmax_block(ChainDev *g, unsigned long lo
                 if (r[q] == best) {
                     const uint32_t sl = 4 * i + (uint32_t)q;
                     const unsigned long long k = hkey[sl];
-                    const unsigned long long tw = tie_of<SEEDED>((uint32_t)k, (uint32_t)(k >> 32), (int)hidx[sl], seed);
+                    const unsigned long long tw = tie_of<SEEDED>((uint32_t)k, (uint32_t)(k >> 32), (int)hidx[sl], seed, order);
                     bt = tw > bt ? tw : bt;
                 }
         }
@@ -1087,13 +1093,15 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ void searc
     unsigned long long sp_word = g->spec[par ^ 1].word, sp_tie = g->spec[par ^ 1].tie;
     unsigned int cn_prev = g->c_n[par ^ 1];
     Ctx c = make_ctx_raw<SEEDED>(g, 2 * step);
+    uint32_t ord = 0;  // the chain's seeded tie order (SEEDED instantiations)
+    if constexpr (SEEDED) ord = g->tie_order;
     const DA_GLOBAL da_u2 *rowoff = (const DA_GLOBAL da_u2 *)g->rowoff;
     const DA_GLOBAL CandEntry *cl_prev = (const DA_GLOBAL CandEntry *)&g->c_list[par ^ 1][0];
     DA_GLOBAL CandEntry *ll_out = (DA_GLOBAL CandEntry *)&g->l_list[par][0];
     pin_sgpr(was_done, had_error, n_groups, sp_word, sp_tie, cn_prev);
     pin_sgpr(c.gs_log2, c.cmask, c.hkey, c.hrank, c.grec, c.rows);
     pin_sgpr(rowoff, cl_prev, ll_out);
-    if constexpr (SEEDED) pin_sgpr(c.seed);
+    if constexpr (SEEDED) pin_sgpr(c.seed, ord);
     if (was_done || had_error != E_OK) return;  // (the substitution block stops the chain)
     __shared__ unsigned long long q_floor, q_red_tie[NW], q_ub[GPL][SEL2_THREADS];
     __shared__ uint32_t q_work[MAX_GROUPS];  // groups still to be read after round 0: index into q_ub | dirty << 31
@@ -1112,7 +1120,7 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ void searc
     bool from_spec;
     const bool fast = resolve_pick(cl_prev, sp_word, sp_tie, cn_prev, pk_tie, from_spec);
     uint32_t exA = ROW_NONE, exB = ROW_NONE;  // rows whose entries the pass leaves out
-    if (fast) tie_rows<SEEDED>(pk_tie, c.seed, exA, exB);
+    if (fast) tie_rows<SEEDED>(pk_tie, c.seed, ord, exA, exB);
     unsigned int rescans = 0;
 #ifdef DA_PHASE_TIMERS
     unsigned int q_stale = 0, q_touch = 0, q_rounds = 0;
@@ -1134,7 +1142,7 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ void searc
         // returns the entry's bound word if it counts towards the floor, else 0; fl = the floor at the time (entries of the excluded rows are listed from there on)
         auto offer = [&](uint32_t r, unsigned long long tw, unsigned long long fl, bool list) -> unsigned long long {
             uint32_t i0, i1;
-            tie_rows<SEEDED>(tw, c.seed, i0, i1);
+            tie_rows<SEEDED>(tw, c.seed, ord, i0, i1);
             const bool t0 = i0 == exA || i0 == exB, t1 = i1 == exA || i1 == exB;
             if (!(t0 || t1)) {
                 if (r > nr || (r == nr && tw > nt)) {
@@ -1248,7 +1256,7 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ void searc
                         for (int v = 1; v < RKN; ++v) r = u == v ? rk[v] : r;
                         const uint32_t sl = base + (uint32_t)(lane + u * WAVE);
                         const unsigned long long k = c.hkey[sl];
-                        const unsigned long long tw = tie_of<SEEDED>((uint32_t)k, (uint32_t)(k >> 32), (int)hidx[sl], c.seed);
+                        const unsigned long long tw = tie_of<SEEDED>((uint32_t)k, (uint32_t)(k >> 32), (int)hidx[sl], c.seed, ord);
                         if (r == grank) gt = tw > gt ? tw : gt;
                         lw = max(lw, offer(r, tw, fl, pass != 0));
                     }
@@ -1257,7 +1265,7 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ void searc
                     const uint32_t r2 = c.hrank[base + o];
                     if (r2 >= thr) {
                         const unsigned long long k2 = c.hkey[base + o];
-                        const unsigned long long tw = tie_of<SEEDED>((uint32_t)k2, (uint32_t)(k2 >> 32), (int)hidx[base + o], c.seed);
+                        const unsigned long long tw = tie_of<SEEDED>((uint32_t)k2, (uint32_t)(k2 >> 32), (int)hidx[base + o], c.seed, ord);
                         if (r2 == grank) gt = tw > gt ? tw : gt;
                         lw = max(lw, offer(r2, tw, fl, pass != 0));
                     }
@@ -1345,7 +1353,7 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ void searc
         // every wave fetches list references and records of ITS candidate's rows now (in flight across the reduction)
         uint32_t cA = 0u, cB = 0u;
         if constexpr (SEEDED) {
-            if (wnr) tie_rows<SEEDED>(wnt, c.seed, cA, cB);
+            if (wnr) tie_rows<SEEDED>(wnt, c.seed, ord, cA, cB);
         } else {
             cA = wnr ? (uint32_t)((wnt >> 7) & 0xFFFFFFu) : 0u, cB = wnr ? (uint32_t)(wnt >> 31) : 0u;
         }
@@ -1376,7 +1384,7 @@ template <class Cell, bool SEEDED = false> __device__ __forceinline__ void searc
                 if (lane == 0 && rescans) atomicAdd(&g->st_rescans, (unsigned long long)rescans);
                 return;  // the table holds nothing selectable: the chain ends
             }
-            tie_rows<SEEDED>(best_tie, c.seed, exA, exB);
+            tie_rows<SEEDED>(best_tie, c.seed, ord, exA, exB);
             __threadfence();  // the bounds this pass tightened are re-read by the next one: stores complete, this CU's L1 dropped
             __syncthreads();
         } else {
@@ -1472,6 +1480,8 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false, bool SEEDED = 
     float sp_ra0 = g->spec[par ^ 1].ra.lo, sp_ra1 = g->spec[par ^ 1].ra.hi, sp_ra2 = g->spec[par ^ 1].ra.step, sp_ra3 = g->spec[par ^ 1].ra.lat;
     float sp_rb0 = g->spec[par ^ 1].rb.lo, sp_rb1 = g->spec[par ^ 1].rb.hi, sp_rb2 = g->spec[par ^ 1].rb.step, sp_rb3 = g->spec[par ^ 1].rb.lat;
     Ctx c = make_ctx_raw<SEEDED>(g, 2 * iter);
+    uint32_t ord = 0;  // the chain's seeded tie order (SEEDED instantiations)
+    if constexpr (SEEDED) ord = g->tie_order;
     DA_GLOBAL int *collen = (DA_GLOBAL int *)g->collen;
     DA_GLOBAL da_u2 *rowoff = (DA_GLOBAL da_u2 *)g->rowoff;
     DA_GLOBAL Entry *rl = (DA_GLOBAL Entry *)g->rlist;
@@ -1490,7 +1500,7 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false, bool SEEDED = 
     pin_sgpr(c.n_out, c.n_bits, c.K, c.Kpad, c.rows);
     pin_sgpr(collen, rowoff, rl, mA, mB, mcol, collist, cmap, colbits, pl_ids, plist, picks, sp_cnt);
     if constexpr (SHARDED) pin_sgpr(cs_slab, cs_flags);
-    if constexpr (SEEDED) pin_sgpr(c.seed);
+    if constexpr (SEEDED) pin_sgpr(c.seed, ord);
     const int n_out = c.n_out, Kpad = c.Kpad, nb = c.n_bits;
     // column-sharded chain (cmvm_shard.h): a rank whose chain stops (finished, or an error) still hands out the flag buffer of the step -- zero
     // flags and the status trailer {1, capacity error?, other error?} -- written here, on the device: the host does not read the descriptor
@@ -1561,7 +1571,7 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false, bool SEEDED = 
     bool from_spec;
     const bool fast = resolve_pick(cl_prev, sp_word, sp_tie, cn_prev, best_tie, from_spec);
     uint32_t A, B;
-    tie_rows<SEEDED>(best_tie, c.seed, A, B);
+    tie_rows<SEEDED>(best_tie, c.seed, ord, A, B);
     da_u2 refA = da_u2{sp_ax, sp_ay}, refB = da_u2{sp_bx, sp_by};
     RowInfo ra = RowInfo{sp_ra0, sp_ra1, sp_ra2, sp_ra3}, rb = RowInfo{sp_rb0, sp_rb1, sp_rb2, sp_rb3};
     if (fast && !from_spec) {  // (block-uniform) a listed entry won: its rows' list references and records (one round trip, broadcast loads)
@@ -1601,9 +1611,9 @@ template <class Cell, bool SHARDED = false, bool MANYCOL = false, bool SEEDED = 
         // plain pass over the rank array -- nothing is written, no bound is read, and nothing is awaited from the search block of this launch, which
         // finds the same entry through the bounds for its own purpose (HIP promises nothing about the order in which workgroups are dispatched)
         uint32_t r0;
-        table_argmax_block<SEEDED>(g, c.seed, r0, best_tie, s_am_rank, s_am_tie);
+        table_argmax_block<SEEDED>(g, c.seed, ord, r0, best_tie, s_am_rank, s_am_tie);
         pk_word = r0 ? bound_word(r0, best_tie) : 0ull;
-        tie_rows<SEEDED>(best_tie, c.seed, A, B);
+        tie_rows<SEEDED>(best_tie, c.seed, ord, A, B);
         if (pk_word) {
             refA = rowoff[A];
             refB = rowoff[B];
@@ -2000,6 +2010,7 @@ template <class Cell> struct UpdStep {
     const DA_GLOBAL typename RowFmt<Cell>::Entry *rl;
     const DA_GLOBAL unsigned long long *plist;
     uint32_t dcw;  // the bits of the chain's latency-penalty weight in the WEIGHTED instantiations, unused (0) in the others
+    uint32_t ord;  // the chain's seeded tie order (TIE_ORDER_*) in the SEEDED instantiations, unused (0) in the others
 };
 // ONE round trip: every descriptor field an update worker needs, pinned before the first branch (pin_sgpr)
 template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __forceinline__ UpdStep<Cell> load_upd_step(ChainDev *gq) {
@@ -2014,6 +2025,10 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __f
         u.dcw = f2u(gq->dc_weight);
     else
         u.dcw = 0;
+    if constexpr (SEEDED)
+        u.ord = gq->tie_order;
+    else
+        u.ord = 0;
     // the step being applied is iter - 1 (the selection has counted it): its search left the best entry the step does not touch in
     // spec[(iter - 1) & 1]; the best entry of every block this launch writes that reaches it goes to c_list[(iter - 1) & 1] (fold_entry)
     u.c.rword = gq->spec[(iter - 1) & 1].word;
@@ -2027,7 +2042,7 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __f
     pin_sgpr(u.done, u.n_partners, iter, u.m, u.n_in, u.A, u.B, u.Nw, u.shift, u.sub, u.mcol, u.mA, u.cmap, u.rl, u.plist);
     pin_sgpr(u.c.n_out, u.c.n_bits, u.c.K, u.c.Kpad, u.c.method, u.c.gs_log2, u.c.pb_log2, u.c.cmask, u.c.windows, u.c.hkey, u.c.hrank, u.c.hblk, u.c.grec, u.c.rows);
     pin_sgpr(u.c.rword, u.c.cn, u.c.cl);
-    if constexpr (SEEDED) pin_sgpr(u.c.seed);
+    if constexpr (SEEDED) pin_sgpr(u.c.seed, u.ord);
     if constexpr (WEIGHTED) pin_sgpr(u.dcw);
     u.c.tomb = KEY_TOMB - (unsigned long long)((2 * iter - 1) & 3);
     ctx_finish(u.c);
@@ -2095,7 +2110,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
     using Entry = typename F::Entry;
     constexpr int HW = ((sizeof(Cell) == 4 ? 24 : 60) + HL - 1) / HL;  // count words per lane (a block's words over its HL lanes): narrow layout Kpad / 2 <= 24 words, wide <= 60
     const Ctx &c = u.c;
-    const BlockEval<SEEDED, WEIGHTED> ev{c, u.dcw};
+    const BlockEval<SEEDED, WEIGHTED> ev{c, u.dcw, u.ord};
     const uint32_t A = u.A, B = u.B, Nw = u.Nw;
     const int m = u.m, n_in = u.n_in, pk_shift = u.shift, pk_sub = u.sub;
     const DA_GLOBAL Entry *rl = u.rl;
@@ -2388,7 +2403,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
 template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __forceinline__ void special_pairs(ChainDev *gq, const UpdStep<Cell> &u, int part) {
     const Ctx &c = u.c;
     const uint32_t A = u.A, B = u.B, Nw = u.Nw;
-    const BlockEval<SEEDED, WEIGHTED> ev{c, u.dcw};
+    const BlockEval<SEEDED, WEIGHTED> ev{c, u.dcw, u.ord};
     const DA_GLOBAL uint32_t *spc = (const DA_GLOBAL uint32_t *)gq->sp_cnt;
     const RowInfo ra = load_row(c.rows, A), rb = load_row(c.rows, B), rn = load_row(c.rows, Nw);
     const int lane = lane_id();
@@ -2412,7 +2427,7 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __f
         for (int e = (wave_id() + 2) % UPD_WAVES; e < nl; e += UPD_WAVES) {  // (waves 2 and 3 first: 0 and 1 had a pair)
             const unsigned long long tw = ll[e].tie;
             uint32_t i0, i1;
-            tie_rows<SEEDED>(tw, c.seed, i0, i1);
+            tie_rows<SEEDED>(tw, c.seed, ev.ord, i0, i1);
             const uint32_t r = (i0 == A || i0 == B) ? i1 : i0;
             int hit = 0;
             for (int k = lane; k < u.m; k += WAVE) hit |= (int)((colbits[(size_t)u.mcol[k] * cbw + (r >> 5)] >> (r & 31)) & 1u);
@@ -2519,7 +2534,7 @@ template <class Cell> __global__ void __launch_bounds__(256) k_cs_init_table(Cha
         if (lane_id() == 0) g->unknown_hit = 1;
         return;
     }
-    table_insert(BlockEval<false, false>{c, 0u}, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return (uint32_t)cnt[k]; });
+    table_insert(BlockEval<false, false>{c, 0u, 0u}, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return (uint32_t)cnt[k]; });
 }
 
 // one block: union of the partner rows of all ranks (summed flag fields != 0), ascending row ids -> cs_uni, cs_nuni
@@ -2626,7 +2641,7 @@ template <class Cell> __global__ void __launch_bounds__(256) k_cs_apply(ChainDev
     c.rword = g->spec[(g->iter - 1) & 1].word;
     c.cn = &g->c_n[(g->iter - 1) & 1];
     c.cl = &g->c_list[(g->iter - 1) & 1][0];
-    const BlockEval<false, false> ev{c, 0u};  // (the sharded kernels have no SEEDED / WEIGHTED instantiations)
+    const BlockEval<false, false> ev{c, 0u, 0u};  // (the sharded kernels have no SEEDED / WEIGHTED instantiations)
     const int K = c.K;
     const int w = (int)blockIdx.x * 4 + wave_id();
     const uint32_t A = g->A, B = g->B, Nw = g->Nw;
@@ -2641,7 +2656,7 @@ template <class Cell> __global__ void __launch_bounds__(256) k_cs_apply(ChainDev
             for (int e = 0; e < nl; ++e) {
                 const unsigned long long tw = ll[e].tie;
                 uint32_t i0, i1;
-                tie_rows<false>(tw, c.seed, i0, i1);
+                tie_rows<false>(tw, c.seed, 0u, i0, i1);
                 const uint32_t r = (i0 == A || i0 == B) ? i1 : i0;
                 if (((g->cs_flags[r >> 2] >> (8 * (r & 3))) & 0xFF) == 0) fold_entry(c, (uint32_t)ll[e].rank, tw);
             }

@@ -54,6 +54,7 @@ struct ChainJob {
     int adder_size = -1, carry_size = -1;
     uint64_t tie_seed = 0;  // 0: equal scores are settled as the reference settles them; else by the seeded tie order of cmvm_core.h (a random restart of the greedy search)
     float dc_weight = -1.0f;  // latency-penalty weight of a -dc / -pdc method (entry_rank, cmvm_core.h): finite and >= 0, or negative: the method's own constant.  Other methods ignore it; column-sharded chains keep the constant
+    uint32_t tie_order = TIE_ORDER_RANDOM;  // which seeded order a chain with tie_seed != 0 runs (TIE_ORDER_*, cmvm_core.h); means nothing with tie_seed == 0
 };
 struct ChainOut {
     int error = E_OK;
@@ -93,6 +94,7 @@ struct SolveOptions {
     bool search_all = true;
     uint64_t seed = 0;  // tie seed of every greedy chain of the problem (0: the reference's result)
     float dc_weight = -1.0f;  // latency-penalty weight of every greedy chain of the problem whose method is mc-dc, mc-pdc, wmc-dc or wmc-pdc; negative: unset, the reference's constant per method
+    uint32_t tie_order = TIE_ORDER_RANDOM;  // seeded tie order of every greedy chain of the problem (TIE_ORDER_*); with seed 0 it is normalised to RANDOM: seed 0 is the reference whatever the order says
 };
 
 int parse_method(const std::string &name);  // da::Method or -1

@@ -120,6 +120,7 @@ void fill_job(ChainDev &d, const ChainJob &j, int n_loc, int col0, unsigned char
     d.col0 = col0;
     d.method = j.method;
     d.tie_seed = j.tie_seed;
+    d.tie_order = j.tie_seed ? j.tie_order : TIE_ORDER_RANDOM;
     d.dc_weight = chain_dc_weight(j);
     d.adder_size = j.adder_size;
     d.carry_size = j.carry_size;

@@ -23,6 +23,7 @@
 #ifndef DA4ML_HIP_H
 #define DA4ML_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -107,15 +108,28 @@ int da_solve_batch_seeded(int count, const float *const *kernels, const int64_t 
  * its own matrix and options, whatever else the batch holds and wherever it stands in it.  da_solve_batch_seeded, da_solve_batch and
  * da_solve are this call with equal structs.  Small weights trade latency for adders between wmc and wmc-dc;
  * da4ml_amd.cmvm.solve_tradeoff sweeps them in one call and returns the Pareto front.  Column-sharded solves keep the constants.
- * struct_size must be sizeof(da_solve_opts). */
+ * tie_order (addition, no reference counterpart): which strict total order a problem with seed != 0 settles equal scores by.
+ *   DA_TIE_RANDOM  the order of da_solve_batch_seeded: a keyed bijection of the whole row pair -- which pair wins a tie is random.
+ *   DA_TIE_NEWEST  the reference lets the pair with the larger (id1, id0) win, i.e. the pair that re-uses the newest row; this order keeps
+ *                  that -- the larger id1 still wins -- and orders the pairs of one id1, and the keys of one pair, by the seed.
+ * Contract: with seed 0 the result is the reference's, bit for bit, whatever tie_order says; a (seed, tie_order) pair gives the same
+ * result on every run, in every batch composition and position; any other tie_order gives DA_ERR_VALUE ("tie_order must be
+ * DA_TIE_RANDOM or DA_TIE_NEWEST").  da_solve_batch_seeded stays the random order.  Column-sharded solves take neither.
+ * struct_size must be sizeof(da_solve_opts), or DA_SOLVE_OPTS_SIZE_V1 -- the struct as it was before tie_order, its last field, was
+ * added: tie_order is then not read and the problem runs DA_TIE_RANDOM.  Any other size gives DA_ERR_VALUE.  The structs of one call
+ * lie struct_size bytes apart (an array of the caller's struct): all of one call have the same struct_size. */
 #define DA_DC_WEIGHT_DEFAULT (-1.0f)
+#define DA_TIE_RANDOM 0u
+#define DA_TIE_NEWEST 1u
 typedef struct da_solve_opts {
     uint32_t struct_size;
     const char *method0, *method1;
     int hard_dc, decompose_dc, adder_size, carry_size, search_all_decompose_dc;
     float dc_weight;
     uint64_t seed;
+    uint32_t tie_order;
 } da_solve_opts;
+#define DA_SOLVE_OPTS_SIZE_V1 ((uint32_t)offsetof(da_solve_opts, tie_order))
 int da_solve_batch_opts(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const da_solve_opts *opts /* [count] */,
                         const float *const *qintervals, const float *const *latencies, da_result **results);
 
