@@ -29,7 +29,8 @@ EXPORTS = (
     'da_last_error da_last_error_code da_version da_device_count da_set_device da_get_lsb_loc da_iceil_log2 da_cost_add da_int_arr_to_csd '
     'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_batch_seeded da_solve_batch_opts da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
     'da_result_stats da_free da_timings da_engine_stats da_dais_run da_dais_last_error da_dais_run_on '
-    'da_dais_compile da_dais_exec_info da_dais_exec_scratch da_dais_exec_run da_dais_exec_free'
+    'da_dais_compile da_dais_exec_info da_dais_exec_scratch da_dais_exec_run da_dais_exec_free '
+    'da_dais_exec_run_mode da_dais_exec_info2 da_dais_exec_level_schedule'
 ).split()
 
 
@@ -576,6 +577,15 @@ def dais_interp_run(bin_logic, data, n_threads: int = 1, executor: str = 'host')
 
 _DAIS_RESIDENT = 3  # DA_DAIS_DEVICE_RESIDENT
 _DAIS_TYPES = {np.dtype(np.float64): 0, np.dtype(np.float32): 1}  # DA_DAIS_F64 / DA_DAIS_F32
+_DAIS_MODES = {'auto': 0, 'sample': 1, 'level': 2}  # DA_DAIS_MODE_*
+_DAIS_LAST_RUN = {-1: 'none', 0: 'sample', 1: 'level-lds', 2: 'level-global'}
+
+
+def dais_mode_code(mode) -> int:
+    """``DA_DAIS_MODE_*`` of a mode's name; anything else is a ``ValueError``"""
+    if not isinstance(mode, str) or mode not in _DAIS_MODES:
+        raise ValueError(f'unknown DAIS execution mode {mode!r} (one of {sorted(_DAIS_MODES)})')
+    return _DAIS_MODES[mode]
 
 
 def _is_torch_tensor(x) -> bool:
@@ -607,7 +617,13 @@ class DaisExecutable:
     ``data_ptr()``, queued on ``torch.cuda.current_stream()`` with no synchronisation (on torch's default stream, which has no handle to
     queue on, the call waits for the stream and for its own run instead; a chain with lookup tables always waits, to report a lookup out of
     bounds).  ``out``: an array / tensor ``[n, n_out]`` to write into (a slice of a wider one will do).  One handle's resident runs belong on
-    one stream at a time: they share the handle's scratch memory."""
+    one stream at a time: they share the handle's scratch memory.
+
+    ``mode``: ``'sample'`` runs the statements in program order, one thread per sample (``k_dais_exec``: a call takes as long as the
+    statement list is, however few the rows); ``'level'`` runs them by dependency level, the lanes of a workgroup over the statements of
+    a level (``k_dais_exec_level``: a small batch takes as long as the graph is deep); ``'auto'`` (default) is the library's rule
+    (include/da4ml_hip.h).  The bits are the same.  With ``executor='host-scalar'``, ``'level'`` walks the level schedule on the host
+    (test aid); ``'host'`` ignores the mode."""
 
     def __init__(self, programs):
         progs = [np.ascontiguousarray(np.ravel(p), dtype=np.int32) for p in programs]
@@ -617,6 +633,9 @@ class DaisExecutable:
         L.da_dais_exec_info.argtypes = [C.c_void_p, _i64p]
         L.da_dais_exec_scratch.argtypes = [C.c_void_p, _i64p]
         L.da_dais_exec_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        L.da_dais_exec_run_mode.argtypes = L.da_dais_exec_run.argtypes + [C.c_int]
+        L.da_dais_exec_info2.argtypes = [C.c_void_p, _i64p, C.c_int]
+        L.da_dais_exec_level_schedule.argtypes = [C.c_void_p, _i64p, C.c_void_p]
         L.da_dais_exec_free.argtypes = [C.c_void_p]
         L.da_dais_last_error.restype = C.c_char_p
         self._h = None
@@ -635,10 +654,22 @@ class DaisExecutable:
     @property
     def info(self) -> dict:
         """what ``da_dais_exec_info`` and ``da_dais_exec_scratch`` report: sizes, slot count, register-file variant; address and bytes of
-        the register-file scratch on the device and the device allocations runs have made so far"""
+        the register-file scratch on the device and the device allocations runs have made so far; of ``da_dais_exec_info2`` the level
+        schedule (``n_levels``, ``level_width``: statements in the widest level, ``level_slots``) and the last device run (``last_run``:
+        ``'none'``, ``'sample'``, ``'level-lds'`` or ``'level-global'``; ``level_S``: samples per tile of the last level run)"""
         s = np.zeros(3, np.int64)
         lib().da_dais_exec_scratch(self._handle(), s)
-        return dict(self._static, scratch_ptr=int(s[0]), scratch_bytes=int(s[1]), allocations=int(s[2]))
+        v = np.zeros(5, np.int64)
+        lib().da_dais_exec_info2(self._handle(), v, 5)
+        return dict(self._static, scratch_ptr=int(s[0]), scratch_bytes=int(s[1]), allocations=int(s[2]), n_levels=int(v[0]), level_width=int(v[1]),
+                    level_slots=int(v[2]), last_run=_DAIS_LAST_RUN[int(v[3])], level_S=int(v[4]))  # fmt: skip
+
+    def level_schedule(self):
+        """``da_dais_exec_level_schedule``: (rows ``[n_ops, 6]`` in the schedule's order = statement number in program order over the chain,
+        level, slot written, slots read a / b / c or -1; slots of the outputs ``[n_out]``, -1 for an absent one)"""
+        rows, outs = np.zeros((self._static['n_ops'], 6), np.int64), np.zeros(max(self.n_out, 1), np.int64)
+        lib().da_dais_exec_level_schedule(self._handle(), rows.reshape(-1) if rows.size else np.zeros(1, np.int64), outs.ctypes.data)
+        return rows, outs[: self.n_out]
 
     def _handle(self):
         if self._h is None:
@@ -662,14 +693,15 @@ class DaisExecutable:
         except Exception:  # interpreter shutdown
             pass
 
-    def _run(self, where, xp, xt, xs, n, yp, yt, ys, n_threads, stream):
+    def _run(self, where, xp, xt, xs, n, yp, yt, ys, n_threads, stream, mode=0):
         L = lib()
-        if L.da_dais_exec_run(self._handle(), xp, xt, xs, n, yp, yt, ys, int(n_threads), where, stream) != 0:
+        if L.da_dais_exec_run_mode(self._handle(), xp, xt, xs, n, yp, yt, ys, int(n_threads), where, stream, mode) != 0:
             raise RuntimeError(L.da_dais_last_error().decode())
 
-    def __call__(self, x, out=None, out_dtype=None, executor: str = 'device', n_threads: int = 0):
+    def __call__(self, x, out=None, out_dtype=None, executor: str = 'device', n_threads: int = 0, mode: str = 'auto'):
+        mode = dais_mode_code(mode)
         if _is_torch_tensor(x):
-            return self._call_torch(x, out, out_dtype, executor)
+            return self._call_torch(x, out, out_dtype, executor, mode)
         if executor not in _DAIS_EXECUTORS:
             raise ValueError(f'unknown DAIS executor {executor!r} (one of {sorted(_DAIS_EXECUTORS)})')
         x = np.asarray(x)
@@ -692,10 +724,10 @@ class DaisExecutable:
         ys = _np_rows(out, self.n_out)
         if ys is None or not out.flags.writeable:
             raise ValueError('out must be writeable with rows that are contiguous in the last dimension')
-        self._run(_DAIS_EXECUTORS[executor], x.ctypes.data, _DAIS_TYPES[x.dtype], xs, n, out.ctypes.data, _DAIS_TYPES[out.dtype], ys, n_threads, None)
+        self._run(_DAIS_EXECUTORS[executor], x.ctypes.data, _DAIS_TYPES[x.dtype], xs, n, out.ctypes.data, _DAIS_TYPES[out.dtype], ys, n_threads, None, mode)
         return out
 
-    def _call_torch(self, x, out, out_dtype, executor):
+    def _call_torch(self, x, out, out_dtype, executor, mode=0):
         import torch
 
         types = {torch.float64: 0, torch.float32: 1}
@@ -728,7 +760,7 @@ class DaisExecutable:
             stream = torch.cuda.current_stream()
             if not stream.cuda_stream:  # torch's default stream is the null stream: nothing to queue on
                 stream.synchronize()
-            self._run(_DAIS_RESIDENT, x.data_ptr(), types[x.dtype], xs, n, out.data_ptr(), types[out.dtype], ys, 0, stream.cuda_stream or None)
+            self._run(_DAIS_RESIDENT, x.data_ptr(), types[x.dtype], xs, n, out.data_ptr(), types[out.dtype], ys, 0, stream.cuda_stream or None, mode)
         return out
 
 

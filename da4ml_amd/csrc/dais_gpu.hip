@@ -9,6 +9,9 @@
 // n_ops -- small enough for a tile of 10^5-10^6 samples to stay L2/MALL resident between producer and consumer steps.
 // The decoded steps are uniform across the grid: the compiler reads them with scalar loads, the switch is a uniform
 // branch.  Per-value arithmetic is dais::eval of dais_core.h, the same code the host executor is tested with.
+//
+// A compiled executable (second half of the file) has a second kernel for small batches, k_dais_exec_level: a workgroup runs the
+// statements of a dependency level side by side, so that a call lasts as long as the graph is deep, not as long as its list.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -218,6 +221,69 @@ void dais_run_gpu(const dais::Program &g, const double *inputs, int64_t n_sample
 // uploaded once; k_dais_exec runs all stages of a sample in one thread and one launch.
 // ================================================================================================================================
 
+namespace {
+
+// Chain::lv (dais_exec.h) from the chain's statements (c.steps: everything but the slots), the values every statement reads and the
+// values behind the outputs of the last stage (-1: absent)
+void build_levels(dais::Chain &c, const std::vector<std::array<int64_t, 3>> &opnd, const std::vector<int64_t> &out_value) {
+    using namespace dais;
+    const int64_t total = (int64_t)c.steps.size();
+    LevelSchedule &lv = c.lv;
+    std::vector<int32_t> level((size_t)total, 0), dies((size_t)total, -1);  // dies: the level of a value's last reader
+    int32_t n_levels = 0;
+    for (int64_t v = 0; v < total; ++v) {  // (a statement's operands precede it: causality inside a stage, the stage order across)
+        for (int64_t r : opnd[v])
+            if (r >= 0) level[v] = std::max(level[v], level[r] + 1);
+        for (int64_t r : opnd[v])
+            if (r >= 0) dies[r] = std::max(dies[r], level[v]);
+        n_levels = std::max(n_levels, level[v] + 1);
+    }
+    for (int64_t v = 0; v < total; ++v)
+        if (dies[v] < 0) dies[v] = level[v];  // never read: gone with its own level
+    for (int64_t o : out_value)
+        if (o >= 0) dies[o] = n_levels;  // read by the output stage: never released
+    lv.value.resize((size_t)total);
+    for (int64_t v = 0; v < total; ++v) lv.value[v] = (int32_t)v;
+    std::stable_sort(lv.value.begin(), lv.value.end(), [&](int32_t p, int32_t q) {
+        return level[p] != level[q] ? level[p] < level[q] : c.steps[p].s.kind < c.steps[q].s.kind;  // by kind: fewer divergent lanes in dais::eval
+    });
+    lv.level_off.assign((size_t)n_levels + 1, 0);
+    for (int64_t v = 0; v < total; ++v) ++lv.level_off[level[v] + 1];
+    for (int32_t l = 0; l < n_levels; ++l) {
+        lv.widest = std::max<int64_t>(lv.widest, lv.level_off[l + 1]);
+        lv.level_off[l + 1] += lv.level_off[l];
+    }
+    std::vector<std::vector<int32_t>> dying((size_t)n_levels + 1);
+    for (int64_t v = 0; v < total; ++v) dying[dies[v]].push_back((int32_t)v);
+    std::vector<int32_t> slot_of((size_t)total, -1), free_slots;
+    int64_t n_slots = 0;
+    lv.steps.resize((size_t)total);
+    for (int32_t l = 0; l < n_levels; ++l) {
+        // free_slots holds what levels < l released; what dies in l comes back only when all of l has its slots
+        for (int64_t i = lv.level_off[l]; i < lv.level_off[l + 1]; ++i) {
+            const int32_t v = lv.value[i];
+            ChainStep d = c.steps[v];
+            const std::array<int64_t, 3> &r = opnd[v];
+            if (r[0] >= 0) (d.s.kind == K_INPUT ? d.src : d.s.a) = slot_of[r[0]];
+            if (r[1] >= 0) d.s.b = slot_of[r[1]];
+            if (r[2] >= 0) d.s.c = slot_of[r[2]];
+            if (!free_slots.empty()) {
+                d.dst = free_slots.back();
+                free_slots.pop_back();
+            } else
+                d.dst = (int32_t)n_slots++;
+            slot_of[v] = d.dst;
+            lv.steps[i] = d;
+        }
+        for (int32_t v : dying[l]) free_slots.push_back(slot_of[v]);
+    }
+    lv.n_slots = std::max<int64_t>(n_slots, 1);
+    lv.outs = c.outs;
+    for (size_t j = 0; j < lv.outs.size(); ++j) lv.outs[j].slot = out_value[j] < 0 ? -1 : slot_of[out_value[j]];
+}
+
+}  // namespace
+
 dais::Chain dais::build_chain(const std::vector<Program> &stages) {
     const int S = (int)stages.size();
     if (S < 1) throw std::runtime_error("a DAIS executable needs at least one program");
@@ -301,6 +367,9 @@ dais::Chain dais::build_chain(const std::vector<Program> &stages) {
     const Program &e = stages[S - 1];
     c.outs.resize((size_t)e.n_out);
     for (int64_t j = 0; j < e.n_out; ++j) c.outs[j] = ChainOut{e.out_idx[j] < 0 ? -1 : slot_of[base[S - 1] + e.out_idx[j]], e.out_neg[j], e.out_scale[j]};
+    std::vector<int64_t> out_value((size_t)e.n_out);
+    for (int64_t j = 0; j < e.n_out; ++j) out_value[j] = e.out_idx[j] < 0 ? -1 : base[S - 1] + e.out_idx[j];
+    build_levels(c, opnd, out_value);
     return c;
 }
 
@@ -354,6 +423,72 @@ __global__ __launch_bounds__(TPB) void k_dais_exec(const dais::ChainStep *__rest
     }
 }
 
+// The level-parallel executor: a workgroup runs a TILE of S = 1 << log2s samples through the statements of the level schedule
+// (dais_exec.h: LevelSchedule), the lanes of the block over (statement of the current level, sample of the tile), one block barrier
+// between levels.  The duration of a call no longer grows with the length of the statement list but with its depth -- the graphs
+// of a solve are some ten levels deep and thousands of statements wide.  Value file [slot][S] of int64: FILE_IN_LDS in the block's
+// dynamic LDS, otherwise in the block's part of a scratch in global memory, `file` = [block][slot][S], which only the wavefronts
+// of this one workgroup exchange: __syncthreads() is a workgroup-scope release/acquire for global memory too, and the waves of a
+// workgroup share one CU and its vector L1 (the property the many-column carve of k_iter_select2 rests on).
+// The grid is persistent: a block loops over tiles.  Every value is computed by the code of k_dais_exec above.
+constexpr int LV_TPB = 1024;    // largest (and default) block
+constexpr int LV_S_MAX = 16;    // samples per tile, at most
+constexpr int LV_WAVES_CU = 32; // wavefronts a CU keeps resident
+template <class In, class Out, bool FILE_IN_LDS>
+__global__ __launch_bounds__(LV_TPB) void k_dais_exec_level(const dais::ChainStep *__restrict__ steps, const int32_t *__restrict__ level_off, int n_levels,
+                                                            const dais::ChainOut *__restrict__ outs, int n_out, const int32_t *__restrict__ tables,
+                                                            const In *__restrict__ x, int64_t x_stride, Out *__restrict__ y, int64_t y_stride, int64_t *file,
+                                                            int64_t n_slots, int log2s, int64_t n, int64_t n_tiles, unsigned long long *__restrict__ lut_fault) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int S = 1 << log2s;
+    int64_t *R = FILE_IN_LDS ? reinterpret_cast<int64_t *>(smem) : file + ((int64_t)blockIdx.x * n_slots << log2s);
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t s0 = tile << log2s;
+        const int live = n - s0 < S ? (int)(n - s0) : S;  // samples of this tile
+        for (int l = 0; l < n_levels; ++l) {
+            const int lo = level_off[l], work = (level_off[l + 1] - lo) << log2s;
+            for (int w = (int)threadIdx.x; w < work; w += (int)blockDim.x) {
+                const int k = w & (S - 1);
+                if (k >= live) continue;
+                const dais::ChainStep &d = steps[lo + (w >> log2s)];
+                const dais::Step &s = d.s;
+                const int rd = dais::reads(s.kind);
+                const int64_t a = (rd & 1) ? R[(s.a << log2s) + k] : 0;
+                const int64_t b = (rd & 2) ? R[(s.b << log2s) + k] : 0;
+                const int64_t c = (rd & 4) ? R[(s.c << log2s) + k] : 0;
+                int64_t v;
+                if (s.kind == dais::K_LUT) {
+                    const int64_t idx = dais::lut_index(s, a);
+                    if (idx < 0 || idx >= d.tab_len) {
+                        // as k_dais_exec: record the first offending index and keep going with 0
+                        atomicCAS(lut_fault, 0ull, (1ull << 63) | ((unsigned long long)(uint32_t)d.tab_len << 32) | (unsigned long long)(uint32_t)idx);
+                        v = 0;
+                    } else
+                        v = tables[d.tab_off + idx];
+                } else {
+                    double xin = 0.0;
+                    if (s.kind == dais::K_INPUT) {
+                        if (d.src == dais::SRC_EXTERNAL)
+                            xin = (double)x[(s0 + k) * x_stride + s.a];
+                        else if (d.src >= 0)
+                            xin = dais::out_value(R[(d.src << log2s) + k], d.src_neg, d.src_scale);
+                    }
+                    v = dais::eval(s, a, b, c, xin);
+                }
+                R[(d.dst << log2s) + k] = v;
+            }
+            __syncthreads();  // the values of level l are there for level l + 1 (and for the outputs)
+        }
+        const int n_y = n_out * live;
+        for (int w = (int)threadIdx.x; w < n_y; w += (int)blockDim.x) {  // consecutive lanes, consecutive elements of a row
+            const int k = w / n_out, j = w - k * n_out;
+            const dais::ChainOut o = outs[j];
+            y[(s0 + k) * y_stride + j] = o.slot < 0 ? (Out)0.0 : (Out)dais::out_value(R[(o.slot << log2s) + k], o.neg, o.scale);
+        }
+        __syncthreads();  // the next tile's first level writes slots the outputs were read from
+    }
+}
+
 // grow-only device allocation owned by a handle
 struct Scratch {
     void *p = nullptr;
@@ -383,11 +518,21 @@ struct DaisDevExec {
     int64_t tile_cap = 0;  // samples per launch the memory of the device allows (fixed at creation)
     Scratch regs, x, y;
     int64_t allocations = 0;
+    // the level schedule: its statements, level offsets and outputs; the global value file [block][slot][S] of runs that need one
+    dais::ChainStep *lv_steps = nullptr;
+    int32_t *lv_off = nullptr;
+    dais::ChainOut *lv_outs = nullptr;
+    Scratch lv_file;
+    int cus = 1;            // compute units of the device
+    size_t lds_budget = 0;  // dynamic LDS a block of k_dais_exec_level may ask for
+    int64_t free_bytes = 0; // free device memory at creation
+    int last_run = -1, last_s = 0;  // dais_dev_last
 };
 
 void dais_dev_free(DaisDevExec *d) {
     if (!d) return;
     (void)hipFree(d->steps), (void)hipFree(d->outs), (void)hipFree(d->tables), (void)hipFree(d->fault);
+    (void)hipFree(d->lv_steps), (void)hipFree(d->lv_off), (void)hipFree(d->lv_outs);
     if (d->stream) (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -409,6 +554,100 @@ void launch_typed(DaisDevExec *d, const dais::Chain &c, hipStream_t st, const vo
     else
         out_type == DA_DAIS_F32 ? launch_exec<double, float>(d, c, st, x, x_stride, y, y_stride, pitch, n)
                                 : launch_exec<double, double>(d, c, st, x, x_stride, y, y_stride, pitch, n);
+}
+
+// geometry of a level-mode run of n samples
+struct LevelGeom {
+    bool lds = false;
+    int log2s = 0, tpb = LV_TPB, grid = 1;
+    size_t lds_bytes = 0;
+};
+
+int env_int(const char *name, int fallback) {
+    const char *e = std::getenv(name);
+    return e && *e ? std::atoi(e) : fallback;
+}
+
+// S: the largest power of two <= LV_S_MAX that still leaves every CU a tile (small batches spread over the device, large ones share
+// a statement's record among S lanes), halved until the value file fits: the LDS budget, or 1 GB of global scratch and a quarter of
+// the device's free memory.  DA4ML_DAIS_LEVEL_LDS=0 forces the global file, DA4ML_DAIS_LEVEL_S the tile (a power of two, where the file
+// allows it), DA4ML_DAIS_LEVEL_TPB the block size: experiment and test knobs, read at every run; no result depends on them.
+LevelGeom level_geometry(const DaisDevExec *d, const dais::Chain &c, int64_t n) {
+    LevelGeom g;
+    const int64_t slots = c.lv.n_slots;
+    g.tpb = std::min(LV_TPB, std::max(64, env_int("DA4ML_DAIS_LEVEL_TPB", LV_TPB) / 64 * 64));
+    int s = 1;
+    if (const int forced = env_int("DA4ML_DAIS_LEVEL_S", 0); forced > 0)
+        while (s * 2 <= std::min(forced, 64)) s *= 2;
+    else
+        while (s * 2 <= LV_S_MAX && n / (s * 2) >= d->cus) s *= 2;
+    g.lds = env_int("DA4ML_DAIS_LEVEL_LDS", 1) != 0 && (size_t)slots * 8 <= d->lds_budget;
+    const int per_cu_max = std::max(1, LV_WAVES_CU * 64 / g.tpb);
+    auto grid_for = [&](int s_, int per_cu) { return (int)std::min<int64_t>((n + s_ - 1) / s_, (int64_t)d->cus * per_cu); };
+    if (g.lds) {
+        while (s > 1 && (size_t)slots * s * 8 > d->lds_budget) s /= 2;
+        g.lds_bytes = (size_t)slots * s * 8;
+        g.grid = grid_for(s, (int)std::min<size_t>(per_cu_max, std::max<size_t>(1, d->lds_budget / g.lds_bytes)));
+    } else {
+        const int64_t cap = std::max<int64_t>(std::min<int64_t>((int64_t)1 << 30, d->free_bytes / 4), slots * 8);
+        while (s > 1 && (int64_t)grid_for(s, per_cu_max) * slots * s * 8 > cap) s /= 2;
+        g.grid = grid_for(s, per_cu_max);
+        if ((int64_t)g.grid * slots * s * 8 > cap) g.grid = (int)std::max<int64_t>(1, cap / (slots * s * 8));
+    }
+    while ((1 << g.log2s) < s) ++g.log2s;
+    if (((slots + c.n_out) << g.log2s) >= ((int64_t)1 << 31)) throw std::runtime_error("DAIS level executor: the value file of a tile passes 2^31 entries");
+    return g;
+}
+
+template <class In, class Out>
+void launch_level(DaisDevExec *d, const dais::Chain &c, hipStream_t st, const LevelGeom &g, const void *x, int64_t x_stride, void *y, int64_t y_stride, int64_t n) {
+    const int64_t tiles = (n + (1 << g.log2s) - 1) >> g.log2s;
+    const int grid = (int)std::min<int64_t>(g.grid, tiles);
+    if (g.lds)
+        hipLaunchKernelGGL((k_dais_exec_level<In, Out, true>), dim3((unsigned)grid), dim3((unsigned)g.tpb), g.lds_bytes, st, d->lv_steps, d->lv_off,
+                           (int)c.lv.n_levels(), d->lv_outs, (int)c.n_out, d->tables, (const In *)x, x_stride, (Out *)y, y_stride, (int64_t *)nullptr, c.lv.n_slots,
+                           g.log2s, n, tiles, d->fault);
+    else
+        hipLaunchKernelGGL((k_dais_exec_level<In, Out, false>), dim3((unsigned)grid), dim3((unsigned)g.tpb), 0, st, d->lv_steps, d->lv_off, (int)c.lv.n_levels(),
+                           d->lv_outs, (int)c.n_out, d->tables, (const In *)x, x_stride, (Out *)y, y_stride, (int64_t *)d->lv_file.p, c.lv.n_slots, g.log2s, n,
+                           tiles, d->fault);
+    DAIS_HIP(hipGetLastError());
+}
+
+void launch_level_typed(DaisDevExec *d, const dais::Chain &c, hipStream_t st, const LevelGeom &g, const void *x, int in_type, int64_t x_stride, void *y, int out_type,
+                        int64_t y_stride, int64_t n) {
+    if (in_type == DA_DAIS_F32)
+        out_type == DA_DAIS_F32 ? launch_level<float, float>(d, c, st, g, x, x_stride, y, y_stride, n) : launch_level<float, double>(d, c, st, g, x, x_stride, y, y_stride, n);
+    else
+        out_type == DA_DAIS_F32 ? launch_level<double, float>(d, c, st, g, x, x_stride, y, y_stride, n) : launch_level<double, double>(d, c, st, g, x, x_stride, y, y_stride, n);
+}
+
+// the dynamic LDS the level kernel may ask for beside its static LDS, as sel2_lds_budget (hip_chain_setup.h) works it out for the selection
+// kernel; its LDS instantiations are allowed that much
+int level_device() {
+    int device = 0;
+#if defined(__HIPCC__)  // (the HIP stand-in of the emulated build, tests/emu, has the one device 0 and no call to ask for it)
+    DAIS_HIP(hipGetDevice(&device));
+#endif
+    return device;
+}
+size_t level_lds_budget() {
+    const int device = level_device();
+    hipFuncAttributes fa;
+    DAIS_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dais_exec_level<double, double, true>)));
+    int limit = 0;
+    DAIS_HIP(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    if (limit < 64 * 1024) limit = 64 * 1024;
+    const size_t used = fa.sharedSizeBytes + 256;
+    const size_t budget = (size_t)limit > used ? (size_t)limit - used : 0;
+    if (budget > 64 * 1024) {
+        const int b = (int)budget;
+        DAIS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dais_exec_level<double, double, true>), hipFuncAttributeMaxDynamicSharedMemorySize, b));
+        DAIS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dais_exec_level<double, float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, b));
+        DAIS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dais_exec_level<float, double, true>), hipFuncAttributeMaxDynamicSharedMemorySize, b));
+        DAIS_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dais_exec_level<float, float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, b));
+    }
+    return budget;
 }
 
 }  // namespace
@@ -434,6 +673,14 @@ DaisDevExec *dais_dev_create(const dais::Chain &c) {
         DAIS_HIP(hipMemGetInfo(&free_b, &total_b));
         const int64_t per_sample = c.n_slots * 8 + (c.n_in + c.n_out) * 8;
         d->tile_cap = std::min<int64_t>((int64_t)1 << 22, std::max<int64_t>((int64_t)(free_b / 4) / std::max<int64_t>(per_sample, 1), TPB));
+        upload(&d->lv_steps, c.lv.steps);
+        upload(&d->lv_off, c.lv.level_off);
+        upload(&d->lv_outs, c.lv.outs);
+        d->free_bytes = (int64_t)free_b;
+        d->lds_budget = level_lds_budget();
+        hipDeviceProp_t prop;
+        DAIS_HIP(hipGetDeviceProperties(&prop, level_device()));
+        d->cus = std::max(1, prop.multiProcessorCount);
     } catch (...) {
         dais_dev_free(d);
         throw;
@@ -445,8 +692,10 @@ void dais_dev_scratch(const DaisDevExec *d, int64_t *s3) {
     s3[0] = d ? (int64_t)(intptr_t)d->regs.p : 0, s3[1] = d ? (int64_t)d->regs.bytes : 0, s3[2] = d ? d->allocations : 0;
 }
 
+void dais_dev_last(const DaisDevExec *d, int64_t *l2) { l2[0] = d ? d->last_run : -1, l2[1] = d ? d->last_s : 0; }
+
 void dais_dev_run(DaisDevExec *d, const dais::Chain &c, const void *in, int in_type, int64_t in_stride, int64_t n_samples, void *out, int out_type,
-                  int64_t out_stride, bool resident, void *stream) {
+                  int64_t out_stride, bool resident, void *stream, int mode) {
     if (!d) throw std::runtime_error("no HIP device: the DAIS device executor needs a GPU (the host executor does not)");
     if (n_samples <= 0) return;
     int64_t tile = std::min(n_samples, d->tile_cap);
@@ -454,7 +703,22 @@ void dais_dev_run(DaisDevExec *d, const dais::Chain &c, const void *in, int in_t
         tile = std::max<int64_t>(1, std::min<int64_t>(tile, std::atoll(e)));
     tile = (tile + TPB - 1) / TPB * TPB;
     hipStream_t st = stream ? (hipStream_t)stream : d->stream;
-    d->allocations += d->regs.need((size_t)(c.n_slots * tile) * sizeof(int64_t));
+    const bool level = mode == dais::MODE_LEVEL;
+    LevelGeom g;
+    if (level) {  // one geometry for all tiles of the call: that of a whole tile
+        g = level_geometry(d, c, tile < n_samples ? tile : n_samples);
+        if (!g.lds) d->allocations += d->lv_file.need((size_t)g.grid * (size_t)(c.lv.n_slots << g.log2s) * sizeof(int64_t));
+        d->last_run = g.lds ? 1 : 2, d->last_s = 1 << g.log2s;
+    } else {
+        d->allocations += d->regs.need((size_t)(c.n_slots * tile) * sizeof(int64_t));
+        d->last_run = 0;
+    }
+    auto launch = [&](const void *x, void *y, int64_t n) {
+        if (level)
+            launch_level_typed(d, c, st, g, x, in_type, in_stride, y, out_type, out_stride, n);
+        else
+            launch_typed(d, c, st, x, in_type, in_stride, y, out_type, out_stride, tile, n);
+    };
     const size_t in_sz = elem_size(in_type), out_sz = elem_size(out_type);
     // a tile of host rows is staged as one span of its rows with their stride
     auto span = [](int64_t rows, int64_t stride, int64_t row) { return (size_t)((rows - 1) * stride + row); };
@@ -467,11 +731,11 @@ void dais_dev_run(DaisDevExec *d, const dais::Chain &c, const void *in, int in_t
         const char *xi = (const char *)in + (size_t)(s0 * in_stride) * in_sz;
         char *yo = (char *)out + (size_t)(s0 * out_stride) * out_sz;
         if (resident) {
-            launch_typed(d, c, st, xi, in_type, in_stride, yo, out_type, out_stride, tile, n);
+            launch(xi, yo, n);
             continue;
         }
         if (c.n_in > 0) DAIS_HIP(hipMemcpyAsync(d->x.p, xi, span(n, in_stride, c.n_in) * in_sz, hipMemcpyHostToDevice, st));
-        launch_typed(d, c, st, d->x.p, in_type, in_stride, d->y.p, out_type, out_stride, tile, n);
+        launch(d->x.p, d->y.p, n);
         if (c.n_out > 0) {
             if (out_stride == c.n_out)
                 DAIS_HIP(hipMemcpyAsync(yo, d->y.p, (size_t)(n * c.n_out) * out_sz, hipMemcpyDeviceToHost, st));

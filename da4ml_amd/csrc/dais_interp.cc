@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <memory>
@@ -320,30 +321,45 @@ template <class F> void parallel_samples(int64_t n_samples, int n_threads, F &&b
     if (err) std::rethrow_exception(err);
 }
 
-// One sample through a compiled chain (dais_exec.h): the per-thread code of k_dais_exec, statement for statement
-void run_chain_scalar(const Chain &c, const double *x, double *y, int64_t *reg) {
-    for (const ChainStep &d : c.steps) {
-        const Step &s = d.s;
-        const int rd = reads(s.kind);
-        const int64_t a = (rd & 1) ? reg[s.a] : 0, b = (rd & 2) ? reg[s.b] : 0, cc = (rd & 4) ? reg[s.c] : 0;
-        if (s.kind == K_LUT) {
-            const int64_t idx = lut_index(s, a);
-            if (idx < 0 || idx >= d.tab_len)
-                bad("Logic lookup index out of bounds: index=" + std::to_string(idx) + ", table_size=" + std::to_string(d.tab_len));
-            reg[d.dst] = c.tables[(size_t)(d.tab_off + idx)];
-            continue;
-        }
-        double xin = 0.0;
-        if (s.kind == K_INPUT) {
-            if (d.src == SRC_EXTERNAL)
-                xin = x[s.a];
-            else if (d.src >= 0)
-                xin = out_value(reg[d.src], d.src_neg, d.src_scale);
-        }
-        reg[d.dst] = eval(s, a, b, cc, xin);
+// One statement of a chain for one sample over the register file `reg`: the per-value code of the device kernels
+inline void run_chain_step(const Chain &c, const ChainStep &d, const double *x, int64_t *reg) {
+    const Step &s = d.s;
+    const int rd = reads(s.kind);
+    const int64_t a = (rd & 1) ? reg[s.a] : 0, b = (rd & 2) ? reg[s.b] : 0, cc = (rd & 4) ? reg[s.c] : 0;
+    if (s.kind == K_LUT) {
+        const int64_t idx = lut_index(s, a);
+        if (idx < 0 || idx >= d.tab_len)
+            bad("Logic lookup index out of bounds: index=" + std::to_string(idx) + ", table_size=" + std::to_string(d.tab_len));
+        reg[d.dst] = c.tables[(size_t)(d.tab_off + idx)];
+        return;
     }
+    double xin = 0.0;
+    if (s.kind == K_INPUT) {
+        if (d.src == SRC_EXTERNAL)
+            xin = x[s.a];
+        else if (d.src >= 0)
+            xin = out_value(reg[d.src], d.src_neg, d.src_scale);
+    }
+    reg[d.dst] = eval(s, a, b, cc, xin);
+}
+
+// One sample through a compiled chain (dais_exec.h) in program order: the per-thread code of k_dais_exec, statement for statement
+void run_chain_scalar(const Chain &c, const double *x, double *y, int64_t *reg) {
+    for (const ChainStep &d : c.steps) run_chain_step(c, d, x, reg);
     for (size_t j = 0; j < c.outs.size(); ++j) {
         const ChainOut &o = c.outs[j];
+        y[j] = o.slot < 0 ? 0.0 : out_value(reg[o.slot], o.neg, o.scale);
+    }
+}
+
+// One sample through the level schedule of a chain over ITS slots, every level back to front: the statements of a level run in no
+// particular order on the device, so a slot used twice inside a level, or a statement in too early a level, changes a result here
+void run_chain_levels(const Chain &c, const double *x, double *y, int64_t *reg) {
+    const LevelSchedule &lv = c.lv;
+    for (int64_t l = 0; l < lv.n_levels(); ++l)
+        for (int64_t i = lv.level_off[l + 1]; i-- > lv.level_off[l];) run_chain_step(c, lv.steps[(size_t)i], x, reg);
+    for (size_t j = 0; j < lv.outs.size(); ++j) {
+        const ChainOut &o = lv.outs[j];
         y[j] = o.slot < 0 ? 0.0 : out_value(reg[o.slot], o.neg, o.scale);
     }
 }
@@ -362,6 +378,15 @@ thread_local std::string g_dais_err;
 }  // namespace dais
 
 using namespace dais;
+
+// AUTO, from the table of profiles/dais_level.txt: by level up to 65 536 rows -- there the level kernel's median
+// lies below the sample kernel's minimum on both measured programs, 1.4x at 65 536 rows to 170x at one row; at 10^6 rows it does not -- for
+// chains inside what was measured: at least the 4 955 statements of the smaller program, and at least its 495 statements per level on
+// average (a deep, narrow chain pays a barrier per level and tile).  Everything else runs in program order, one thread per sample.
+int dais::auto_mode(int64_t n_steps, int64_t n_levels, int64_t n_samples) {
+    constexpr int64_t LEVEL_MAX_SAMPLES = 65536, LEVEL_MIN_STEPS = 4955, LEVEL_MIN_MEAN_WIDTH = 495;
+    return n_samples <= LEVEL_MAX_SAMPLES && n_steps >= LEVEL_MIN_STEPS && n_steps >= LEVEL_MIN_MEAN_WIDTH * n_levels ? MODE_LEVEL : MODE_SAMPLE;
+}
 
 // device executor (dais_gpu.hip)
 int64_t dais_assign_slots(const dais::Program &g, std::vector<dais::Step> &steps, std::vector<int32_t> &dst, std::vector<int32_t> &slot_of);
@@ -418,17 +443,18 @@ struct da_dais_exec {
 
 namespace {
 
-// HOST: the block executor stage by stage on blocks of BLOCK samples; HOST_SCALAR: the device's per-value path over the chain's slots
+// HOST: the block executor stage by stage on blocks of BLOCK samples; HOST_SCALAR: the device's per-value path over the chain's slots,
+// in program order or (level) over the level schedule and its slots
 void exec_run_host(const da_dais_exec &h, const void *in, int in_type, int64_t in_stride, int64_t n_samples, void *out, int out_type, int64_t out_stride,
-                   int n_threads, bool scalar) {
+                   int n_threads, bool scalar, bool level) {
     const Chain &c = h.chain;
     parallel_samples(n_samples, n_threads, [&](int64_t lo, int64_t hi) {
         std::vector<double> xa((size_t)(h.widest * BLOCK), 0.0), xb((size_t)(h.widest * BLOCK), 0.0);
         if (scalar) {
-            std::vector<int64_t> slots((size_t)c.n_slots, 0);
+            std::vector<int64_t> slots((size_t)(level ? c.lv.n_slots : c.n_slots), 0);
             for (int64_t s = lo; s < hi; ++s) {
                 for (int64_t j = 0; j < c.n_in; ++j) xa[j] = load_elem(in, in_type, s * in_stride + j);
-                run_chain_scalar(c, xa.data(), xb.data(), slots.data());
+                level ? run_chain_levels(c, xa.data(), xb.data(), slots.data()) : run_chain_scalar(c, xa.data(), xb.data(), slots.data());
                 for (int64_t j = 0; j < c.n_out; ++j) store_elem(out, out_type, s * out_stride + j, xb[j]);
             }
             return;
@@ -485,8 +511,39 @@ int da_dais_exec_scratch(const da_dais_exec *h, int64_t *scratch3) {
     return DA_OK;
 }
 
+int da_dais_exec_info2(const da_dais_exec *h, int64_t *out, int n) {
+    if (!h || !out) return DA_ERR_RUNTIME;
+    int64_t last[2];
+    dais_dev_last(h->dev, last);
+    const int64_t v[5] = {h->chain.lv.n_levels(), h->chain.lv.widest, h->chain.lv.n_slots, last[0], last[1]};
+    for (int i = 0; i < std::min(n, 5); ++i) out[i] = v[i];
+    return DA_OK;
+}
+
+int da_dais_exec_level_schedule(const da_dais_exec *h, int64_t *rows6, int64_t *out_slots) {
+    if (!h || !rows6) return DA_ERR_RUNTIME;
+    const LevelSchedule &lv = h->chain.lv;
+    for (int64_t l = 0; l < lv.n_levels(); ++l)
+        for (int64_t i = lv.level_off[l]; i < lv.level_off[l + 1]; ++i) {
+            const ChainStep &d = lv.steps[(size_t)i];
+            const int rd = reads(d.s.kind);
+            int64_t *r = rows6 + 6 * i;
+            r[0] = lv.value[(size_t)i], r[1] = l, r[2] = d.dst;
+            r[3] = d.s.kind == K_INPUT ? (d.src >= 0 ? d.src : -1) : (rd & 1) ? d.s.a : -1;
+            r[4] = (rd & 2) ? d.s.b : -1, r[5] = (rd & 4) ? d.s.c : -1;
+        }
+    if (out_slots)
+        for (size_t j = 0; j < lv.outs.size(); ++j) out_slots[j] = lv.outs[j].slot;
+    return DA_OK;
+}
+
 int da_dais_exec_run(da_dais_exec *h, const void *in, int in_type, int64_t in_row_stride, int64_t n_samples, void *out, int out_type,
                      int64_t out_row_stride, int n_threads, int where, void *stream) {
+    return da_dais_exec_run_mode(h, in, in_type, in_row_stride, n_samples, out, out_type, out_row_stride, n_threads, where, stream, DA_DAIS_MODE_AUTO);
+}
+
+int da_dais_exec_run_mode(da_dais_exec *h, const void *in, int in_type, int64_t in_row_stride, int64_t n_samples, void *out, int out_type,
+                          int64_t out_row_stride, int n_threads, int where, void *stream, int mode) {
     try {
         if (!h) bad("da_dais_exec_run: no executable");
         const Chain &c = h->chain;
@@ -497,13 +554,22 @@ int da_dais_exec_run(da_dais_exec *h, const void *in, int in_type, int64_t in_ro
                 std::to_string(c.n_in) + ", " + std::to_string(c.n_out) + ")");
         if (where != DA_DAIS_HOST && where != DA_DAIS_HOST_SCALAR && where != DA_DAIS_DEVICE && where != DA_DAIS_DEVICE_RESIDENT)
             bad("da_dais_exec_run: unknown executor " + std::to_string(where));
+        if (mode != DA_DAIS_MODE_AUTO && mode != DA_DAIS_MODE_SAMPLE && mode != DA_DAIS_MODE_LEVEL)
+            bad("da_dais_exec_run_mode: unknown mode " + std::to_string(mode));
         if (n_samples <= 0) return DA_OK;
         if ((!in && c.n_in > 0) || (!out && c.n_out > 0)) bad("da_dais_exec_run: null sample pointer");
         std::lock_guard<std::mutex> lk(h->mu);
-        if (where == DA_DAIS_DEVICE || where == DA_DAIS_DEVICE_RESIDENT)
-            dais_dev_run(h->dev, c, in, in_type, in_row_stride, n_samples, out, out_type, out_row_stride, where == DA_DAIS_DEVICE_RESIDENT, stream);
-        else
-            exec_run_host(*h, in, in_type, in_row_stride, n_samples, out, out_type, out_row_stride, n_threads, where == DA_DAIS_HOST_SCALAR);
+        if (where == DA_DAIS_DEVICE || where == DA_DAIS_DEVICE_RESIDENT) {
+            if (mode == DA_DAIS_MODE_AUTO) {  // DA4ML_DAIS_MODE, read at every run, decides in place of the rule
+                const char *e = std::getenv("DA4ML_DAIS_MODE");
+                const std::string m = e ? e : "";
+                if (!m.empty() && m != "sample" && m != "level") bad("DA4ML_DAIS_MODE is 'sample' or 'level', not '" + m + "'");
+                mode = m == "sample" ? MODE_SAMPLE : m == "level" ? MODE_LEVEL : auto_mode((int64_t)c.steps.size(), c.lv.n_levels(), n_samples);
+            }
+            dais_dev_run(h->dev, c, in, in_type, in_row_stride, n_samples, out, out_type, out_row_stride, where == DA_DAIS_DEVICE_RESIDENT, stream, mode);
+        } else  // (AUTO on the host is the program order)
+            exec_run_host(*h, in, in_type, in_row_stride, n_samples, out, out_type, out_row_stride, n_threads, where == DA_DAIS_HOST_SCALAR,
+                          mode == DA_DAIS_MODE_LEVEL);
         return DA_OK;
     } catch (const std::exception &e) {
         g_dais_err = e.what();

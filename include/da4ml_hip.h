@@ -248,6 +248,37 @@ int da_dais_exec_scratch(const da_dais_exec *h, int64_t *scratch3);
 #define DA_DAIS_DEVICE_RESIDENT 3
 int da_dais_exec_run(da_dais_exec *h, const void *in, int in_type, int64_t in_row_stride, int64_t n_samples, void *out, int out_type,
                      int64_t out_row_stride, int n_threads, int where, void *stream);
+/* The same with an execution mode (da_dais_exec_run is this call with DA_DAIS_MODE_AUTO); every mode gives the same bits.
+ *   DA_DAIS_MODE_SAMPLE  the statements in program order: kernel k_dais_exec, one thread per sample.  The duration of a call follows
+ *                        the LENGTH of the statement list whatever n_samples is;
+ *   DA_DAIS_MODE_LEVEL   the statements by dependency level: kernel k_dais_exec_level, a workgroup runs a tile of S samples (a power of
+ *                        two, at most 16) with its lanes over (statement of the level, sample of the tile) and one barrier between
+ *                        levels, so the duration of a small call follows the DEPTH of the graph.  Level of a statement: 0 when it reads
+ *                        no value, else 1 + the largest level it reads (an inner stage's input reads the producing stage's output value).
+ *                        The schedule has slots of its own: a slot is released when the level of its last reader is complete and handed
+ *                        out to later levels only.  Value file [slot][S] in the workgroup's LDS when it fits beside the kernel's static
+ *                        LDS, otherwise in a global scratch of the handle (allocated at the first such run, grown only when needed);
+ *                        DA4ML_DAIS_LEVEL_LDS=0, read at every run, forces the global file;
+ *   DA_DAIS_MODE_AUTO    LEVEL for n_samples <= 65 536 when the chain has at least 4 955 statements and at least 495 statements per level
+ *                        on average, SAMPLE otherwise: the region in which the measurement (profiles/dais_level.txt, DESIGN.md section
+ *                        10a) shows LEVEL faster -- 1.4x at 65 536 rows to 170x at one row; at 10^6 rows SAMPLE is 1.2x to 2.4x faster.
+ *                        DA4ML_DAIS_MODE=sample|level, read at every run, decides in place of this rule; it does not touch an explicit
+ *                        mode.
+ * The mode applies to DA_DAIS_DEVICE and DA_DAIS_DEVICE_RESIDENT.  With DA_DAIS_HOST_SCALAR, LEVEL runs the level schedule over its slots
+ * on the host, every level back to front (test aid); DA_DAIS_HOST ignores the mode.  An unknown mode is DA_ERR_RUNTIME. */
+#define DA_DAIS_MODE_AUTO 0
+#define DA_DAIS_MODE_SAMPLE 1
+#define DA_DAIS_MODE_LEVEL 2
+int da_dais_exec_run_mode(da_dais_exec *h, const void *in, int in_type, int64_t in_row_stride, int64_t n_samples, void *out, int out_type,
+                          int64_t out_row_stride, int n_threads, int where, void *stream, int mode);
+/* Writes min(n, 5) values: levels of the level schedule, statements in its widest level, its slots, what the last device run of the
+ * handle was (-1: none yet, 0: sample, 1: level with the value file in LDS, 2: level with the global file), samples per tile S of the
+ * last level run (0: none yet) */
+int da_dais_exec_info2(const da_dais_exec *h, int64_t *out, int n);
+/* The level schedule, for inspection: rows6 = [statements in total][6] in the schedule's order = statement number in program order over
+ * the whole chain, level, slot written, slots read (operand a -- for an inner stage's input the producing output's value --, b, c; -1:
+ * none); out_slots (may be NULL) = [n_out] slots of the last stage's outputs (-1: absent) */
+int da_dais_exec_level_schedule(const da_dais_exec *h, int64_t *rows6, int64_t *out_slots);
 void da_dais_exec_free(da_dais_exec *h);
 
 /* ---- instrumentation for the benchmark harness ------------------------------------------------------------- */
