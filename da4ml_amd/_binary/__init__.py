@@ -27,7 +27,7 @@ _i32p = np.ctypeslib.ndpointer(np.int32, flags='C_CONTIGUOUS')
 
 EXPORTS = (
     'da_last_error da_last_error_code da_version da_device_count da_set_device da_get_lsb_loc da_iceil_log2 da_cost_add da_int_arr_to_csd '
-    'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_batch_seeded da_solve_batch_opts da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
+    'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_batch_seeded da_solve_batch_opts da_solve_batch_recode da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
     'da_result_stats da_free da_timings da_engine_stats da_dais_run da_dais_last_error da_dais_run_on '
     'da_dais_compile da_dais_exec_info da_dais_exec_scratch da_dais_exec_run da_dais_exec_free '
     'da_dais_exec_run_mode da_dais_exec_info2 da_dais_exec_level_schedule'
@@ -91,6 +91,8 @@ def lib():
         L.da_solve_batch_seeded.argtypes = L.da_solve_batch.argtypes[:-1] + [C.c_void_p, C.c_void_p]
     if hasattr(L, 'da_solve_batch_opts'):  # (likewise)
         L.da_solve_batch_opts.argtypes = [C.c_int, C.c_void_p, _i64p, _i64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, 'da_solve_batch_recode'):  # (likewise)
+        L.da_solve_batch_recode.argtypes = [C.c_int, C.c_void_p, _i64p, _i64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.da_solve_sharded.restype = C.c_void_p
     L.da_solve_sharded.argtypes = [_f32p, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, _i64p]  # fmt: skip
@@ -335,6 +337,7 @@ def solve_many(
     _stats: bool = False,
     seeds=None,
     tie_order='random',
+    recode='csd',
 ):
     """Solve independent matrices concurrently on the GPU (addition to the reference API; same options as ``solve``).
 
@@ -348,20 +351,26 @@ def solve_many(
     ``tie_order``: which order a seed other than 0 gives -- ``'random'`` (the default) or ``'newest'`` (``DA_TIE_NEWEST``: the pair
     with the newest row still wins a tie, as in the reference; the seed orders what lies below), one name for the whole batch.
     Seed 0 is the reference's result under either.
+
+    ``recode``: the signed-digit form the chains of a problem with a seed other than 0 start from -- ``'csd'`` (the default: the
+    reference's digits), ``'compact'`` or ``'seeded'`` (the coin's seed is the problem's tie seed), see ``solve_each``; one name for the
+    whole batch.  A problem with seed 0 stays the reference's result.
     """
     order = tie_order_code(tie_order)
+    recoded = recode_code(recode) != RECODES['csd']
     ks = [_kernel(k) for k in kernels]
     n = len(ks)
     if n == 0:
         return []
-    if order != TIE_ORDERS['random']:  # (da_solve_batch_seeded stays the random order: the other goes through the per-problem structs)
+    if order != TIE_ORDERS['random'] or recoded:  # (da_solve_batch_seeded stays the random order and the CSD digits: the rest goes through the per-problem structs)
         if seeds is None:
             seeds = [0] * n
         if len(seeds) != n:
             raise ValueError('seeds must hold one entry per kernel')
         shared = dict(method0=method0, method1=method1, hard_dc=hard_dc, decompose_dc=decompose_dc, adder_size=adder_size, carry_size=carry_size,
                       search_all_decompose_dc=search_all_decompose_dc, tie_order=tie_order)  # fmt: skip
-        return solve_each(ks, [dict(shared, seed=s) for s in seeds], qintervals=qintervals, latencies=latencies, _stats=_stats)
+        each = [dict(shared, seed=s, recode=recode, recode_seed=s) if recoded and int(s) else dict(shared, seed=s) for s in seeds]
+        return solve_each(ks, each, qintervals=qintervals, latencies=latencies, _stats=_stats)
     seed_arr = None
     if seeds is not None:
         if len(seeds) != n:
@@ -404,6 +413,22 @@ def tie_order_code(name) -> int:
     return TIE_ORDERS[name]
 
 
+RECODES = {'csd': 0, 'compact': 1, 'seeded': 2}  # DA_RECODE_CSD, DA_RECODE_COMPACT, DA_RECODE_SEEDED
+
+
+def recode_code(name) -> int:
+    """``DA_RECODE_*`` of a digit recoding's name; anything else is a ``ValueError``"""
+    if not isinstance(name, str) or name not in RECODES:
+        raise ValueError(f'recode must be one of {sorted(RECODES)}, not {name!r}')
+    return RECODES[name]
+
+
+class RecodeOpts(C.Structure):
+    """``da_recode_opts`` (include/da4ml_hip.h): the digit recoding of one problem of ``da_solve_batch_recode``"""
+
+    _fields_ = [('struct_size', C.c_uint32), ('mode', C.c_uint32), ('seed', C.c_uint64)]
+
+
 class SolveOpts(C.Structure):
     """``da_solve_opts`` (include/da4ml_hip.h): the options of one problem of ``da_solve_batch_opts``"""
 
@@ -422,7 +447,7 @@ class SolveOpts(C.Structure):
     ]
 
 
-_EACH_DEFAULTS = dict(method0='wmc', method1='auto', hard_dc=-1, decompose_dc=-2, adder_size=-1, carry_size=-1, search_all_decompose_dc=True, seed=0, dc_weight=None, tie_order='random')
+_EACH_DEFAULTS = dict(method0='wmc', method1='auto', hard_dc=-1, decompose_dc=-2, adder_size=-1, carry_size=-1, search_all_decompose_dc=True, seed=0, dc_weight=None, tie_order='random', recode='csd', recode_seed=0)
 
 
 def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool = False):
@@ -431,7 +456,9 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
     ``options``: one dict per kernel of ``solve``'s keywords (``method0``, ``method1``, ``hard_dc``, ``decompose_dc``, ``adder_size``,
     ``carry_size``, ``search_all_decompose_dc``) plus ``seed`` (tie seed, 0: the reference's order) and ``dc_weight`` (latency-penalty
     weight of the ``*-dc`` / ``*-pdc`` selectors: a finite number >= 0, or ``None``: the reference's constant per method) and ``tie_order``
-    (``'random'`` or ``'newest'``: the order a seed other than 0 gives, see ``solve_many``; anything else is a ``ValueError``).  Missing keys
+    (``'random'`` or ``'newest'``: the order a seed other than 0 gives, see ``solve_many``; anything else is a ``ValueError``), and ``recode``
+    / ``recode_seed``: the signed-digit form the problem's chains start from -- ``'csd'`` (the reference's), ``'compact'`` or ``'seeded'``
+    with the coin's seed (``da_solve_batch_recode``; ``da4ml_amd.cmvm.solve_recoded`` is the user-facing entry).  Missing keys
     have ``solve``'s defaults.  ``qintervals`` / ``latencies`` as for ``solve_many``.  The result of a problem depends on nothing but its
     own matrix and options.  ``da4ml_amd.cmvm.solve_tradeoff`` is the user-facing entry for weight sweeps."""
     ks = [_kernel(k) for k in kernels]
@@ -443,6 +470,7 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
     if not hasattr(lib(), 'da_solve_batch_opts'):
         raise RuntimeError(f'{_LIB_PATH} has no da_solve_batch_opts: per-problem options need the library of this revision')
     opts = (SolveOpts * n)()
+    recode = (RecodeOpts * n)()
     for i, given in enumerate(options):
         unknown = set(given) - set(_EACH_DEFAULTS)
         if unknown:
@@ -453,6 +481,7 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
             raise ValueError('dc_weight must be a finite number >= 0')
         opts[i] = SolveOpts(C.sizeof(SolveOpts), o['method0'].encode(), o['method1'].encode(), int(o['hard_dc']), int(o['decompose_dc']), int(o['adder_size']),
                             int(o['carry_size']), int(bool(o['search_all_decompose_dc'])), w, int(o['seed']) & 0xFFFFFFFFFFFFFFFF, tie_order_code(o['tie_order']))  # fmt: skip
+        recode[i] = RecodeOpts(C.sizeof(RecodeOpts), recode_code(o['recode']), int(o['recode_seed']) & 0xFFFFFFFFFFFFFFFF)
     n_in = np.array([k.shape[0] for k in ks], np.int64)
     n_out = np.array([k.shape[1] for k in ks], np.int64)
     kptr = (C.c_void_p * n)(*[k.ctypes.data for k in ks])
@@ -466,7 +495,12 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
             ls.append(None if l is None else l.ctypes.data)
         qptr, lptr = (C.c_void_p * n)(*qs), (C.c_void_p * n)(*ls)
     res = (C.c_void_p * n)()
-    rc = lib().da_solve_batch_opts(n, kptr, n_in, n_out, C.cast(opts, C.c_void_p), qptr, lptr, res)
+    if all(r.mode == RECODES['csd'] for r in recode):  # (the call every batch made before there were recodings)
+        rc = lib().da_solve_batch_opts(n, kptr, n_in, n_out, C.cast(opts, C.c_void_p), qptr, lptr, res)
+    else:
+        if not hasattr(lib(), 'da_solve_batch_recode'):
+            raise RuntimeError(f'{_LIB_PATH} has no da_solve_batch_recode: digit recodings need the library of this revision')
+        rc = lib().da_solve_batch_recode(n, kptr, n_in, n_out, C.cast(opts, C.c_void_p), C.cast(recode, C.c_void_p), qptr, lptr, res)
     if rc != 0:
         _raise(rc)
     return [_collect(res[i], _stats) for i in range(n)]

@@ -5,7 +5,7 @@ from typing import NamedTuple, TypedDict
 
 import numpy as np
 
-from .._binary import kernel_decompose, solve, solve_each, solve_many, tie_order_code
+from .._binary import kernel_decompose, recode_code, solve, solve_each, solve_many, tie_order_code
 from ..types import CombLogic, Op, QInterval
 
 
@@ -48,7 +48,7 @@ def first_strict_minimum(costs) -> int:
     return best
 
 
-def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = False, order: str = 'random', **solve_options):
+def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = False, order: str = 'random', recode: str = 'csd', **solve_options):
     """Best of ``n_restarts`` greedy searches of one matrix (addition to the reference API; ``solve_options`` as for ``solve``).
 
     Most greedy steps have several equally scored pairs, and the reference takes the last of them in its sorted table.
@@ -64,16 +64,56 @@ def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = Fa
     same.  At 64x64 and above no random restart beats ``solve`` while most newest-first restarts do (README).  Anything else is a
     ``ValueError``.
 
+    ``recode``: the signed-digit form the restarts r >= 1 start from (``solve_recoded``).  ``'csd'`` (the default): the reference's digits,
+    as every restart had them so far.  ``'compact'``: the compact digits.  ``'seeded'``: the restart's own seed also draws the coins of
+    its digits.  Restart 0 stays ``solve``.  Anything else is a ``ValueError``.
+
     ``return_all=True``: ``(best_index, [Pipeline, ...], [cost, ...])`` instead of the winning Pipeline."""
     from ..multi_gpu import pipeline_cost_f32
 
     tie_order_code(order)
+    recode_code(recode)
     seeds = restart_seeds(n_restarts, seed)
     if order != 'random':
         solve_options = {**solve_options, 'tie_order': order}
+    if recode != 'csd':
+        solve_options = {**solve_options, 'recode': recode}
     per_kernel = {k: [v] * len(seeds) for k, v in solve_options.items() if k in ('qintervals', 'latencies') and v is not None}
     opts = {k: v for k, v in solve_options.items() if k not in ('qintervals', 'latencies')}
     pipes = solve_many([kernel] * len(seeds), seeds=seeds, **opts, **per_kernel)
+    costs = [pipeline_cost_f32(p) for p in pipes]
+    best = first_strict_minimum(costs)
+    return (best, pipes, costs) if return_all else pipes[best]
+
+
+def solve_recoded(kernel, n: int = 8, seed: int = 0, return_all: bool = False, **solve_options):
+    """Best of ``n`` greedy searches of one matrix that differ in the signed digits they start from (addition to the reference API;
+    ``solve_options``: the keywords of ``solve`` and no others).
+
+    Every chain of the reference starts from the CSD (non-adjacent) digits of the matrix.  That is one of several minimal signed-digit
+    forms: 3 is ``4 - 1`` and also ``2 + 1``, with as many digits, and which form the search starts from changes which digit pairs
+    repeat.  Point 0 is ``solve(kernel, **solve_options)`` itself; point 1 starts from the COMPACT digits (every ``s 0 -s`` of the CSD
+    form, scanned from the top, becomes ``0 s s``); points 2 .. n-1 rewrite only the sites a coin picks, keyed by the coefficient's value
+    and the seed ``restart_seeds(n, seed)[r]`` -- equal coefficients get equal digits wherever they stand.  All points keep the
+    reference's tie order and run in one ``solve_each`` call; the stage-1 distances of the matrix are computed once.  The winner is the
+    first strict minimum of the float32 cost (``multi_gpu.pipeline_cost_f32``), so the result is never dearer than ``solve``'s.
+
+    At 3 to 5 bit weights the compact digits save 1 to 3 % of the adders; at 8 bits they lose (README): a restart dimension, not a
+    default.  ``solve_restarts(..., recode=)`` combines a recoding with the tie-order restarts.
+
+    ``return_all=True``: ``(best_index, [Pipeline, ...], [cost, ...])`` instead of the winning Pipeline."""
+    from ..multi_gpu import pipeline_cost_f32
+
+    for key in ('seed', 'tie_order', 'dc_weight', 'recode', 'recode_seed'):  # (solve takes none of them: point 0 would no longer be solve(kernel, **solve_options))
+        if key in solve_options:
+            raise TypeError(f"solve_recoded() takes solve's keywords: {key!r} is not one of them")
+    seeds = restart_seeds(n, seed)
+    per_kernel = {k: [solve_options[k]] * len(seeds) for k in ('qintervals', 'latencies') if solve_options.get(k) is not None}
+    base = {k: v for k, v in solve_options.items() if k not in ('qintervals', 'latencies')}
+    options = [dict(base)]
+    for r in range(1, len(seeds)):
+        options.append({**base, 'recode': 'compact'} if r == 1 else {**base, 'recode': 'seeded', 'recode_seed': seeds[r]})
+    pipes = solve_each([kernel] * len(seeds), options, **per_kernel)
     costs = [pipeline_cost_f32(p) for p in pipes]
     best = first_strict_minimum(costs)
     return (best, pipes, costs) if return_all else pipes[best]
@@ -143,4 +183,4 @@ def cheapest_within(front, max_latency: float):
     return min(ok, key=lambda p: p.cost)
 
 
-__all__ = ['solve', 'solve_many', 'solve_restarts', 'solve_tradeoff', 'cheapest_within', 'TradeoffPoint', 'QInterval', 'Op', 'CombLogic', 'kernel_decompose', 'solver_options_t']
+__all__ = ['solve', 'solve_many', 'solve_restarts', 'solve_recoded', 'solve_tradeoff', 'cheapest_within', 'TradeoffPoint', 'QInterval', 'Op', 'CombLogic', 'kernel_decompose', 'solver_options_t']

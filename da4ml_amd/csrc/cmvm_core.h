@@ -110,6 +110,51 @@ DA_HD int naf_weight(int32_t x) {
     uint64_t d = (x3 ^ (uint64_t)a) >> 1;
     return popc32((uint32_t)d) + popc32((uint32_t)(d >> 32));
 }
+// ------------------------------------------------------------------------------------ digit recoding
+// The digits a greedy chain STARTS from (no reference counterpart: the reference always starts from the NAF).  The NAF is one of several
+// minimal signed-digit forms of a number (3 = 4 - 1 = 2 + 1); which one the search starts from changes which digit pairs repeat.
+//   RECODE_CSD      naf_masks, bit for bit.
+//   RECODE_COMPACT  from the NAF digits d, for p from (top position - 2) down to 0: a site d[p+2] = s != 0, d[p+1] = 0, d[p] = -s is
+//                   rewritten to d[p+2] = 0, d[p+1] = s, d[p] = s  (4s - s = 2s + s).  The scan runs top down, so a site that a rewrite
+//                   creates below it is seen: 11 = 16 - 4 - 1 -> 8 + 4 - 1 -> 8 + 2 + 1.
+//   RECODE_SEEDED   the same scan; a site at p is rewritten only when its coin is 1:
+//                       coin(seed, |x|, p) = splitmix64(splitmix64(seed) ^ ((uint64_t)|x| << 5 | p)) >> 63
+//                   with splitmix64 as da4ml_amd.cmvm.splitmix64 has it.  The coin is keyed by the coefficient's VALUE, not by where it
+//                   stands: equal values get equal digits wherever they stand (a coin per matrix entry loses the sharing between them).
+// The scan works on the digits of |x| and mirrors them for x < 0: x and -x get mirrored digits.  A rewrite preserves the value and the
+// digit count and touches nothing above p + 2: the top position is never raised, so csd_width, naf_weight and everything sized by them
+// hold for every mode.
+constexpr uint32_t RECODE_CSD = 0, RECODE_COMPACT = 1, RECODE_SEEDED = 2, RECODE_COUNT = 3;
+DA_HD uint64_t splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+DA_HD void digit_masks(int32_t x, uint32_t mode, uint64_t seed, uint32_t &plus, uint32_t &minus) {
+    naf_masks(x, plus, minus);
+    if (mode == RECODE_CSD) return;
+    uint32_t same = x < 0 ? minus : plus, opp = x < 0 ? plus : minus;  // the digits of |x|: +1 | -1
+    if (!(same | opp)) return;
+    const uint32_t a = x < 0 ? (uint32_t)(-(int64_t)x) : (uint32_t)x;
+    const uint64_t key = mode == RECODE_SEEDED ? splitmix64(seed) : 0;
+    int top = 31;
+    while (!(((same | opp) >> top) & 1u)) --top;
+    for (int p = top - 2; p >= 0; --p) {
+        const uint32_t hi = 4u << p, mid = 2u << p, lo = 1u << p;
+        if ((same | opp) & mid) continue;
+        const bool up = (same & hi) && (opp & lo), down = (opp & hi) && (same & lo);  // s = +1 | s = -1
+        if (!up && !down) continue;
+        if (mode == RECODE_SEEDED && !(splitmix64(key ^ (((uint64_t)a << 5) | (uint64_t)p)) >> 63)) continue;
+        if (up)
+            same = (same & ~hi) | mid | lo, opp &= ~lo;
+        else
+            opp = (opp & ~hi) | mid | lo, same &= ~lo;
+    }
+    plus = x < 0 ? opp : same;
+    minus = x < 0 ? same : opp;
+}
+
 // digit width N = max(1, ceil(log2(max(maxabs,1) * 1.5)))  (bit_decompose.cc:24-27), in exact integers:
 // the smallest N >= 1 with 2^(N+1) >= 3 * maxabs (3*maxabs is never a power of two, so no rounding case).
 DA_HD int csd_width(uint32_t max_abs) {

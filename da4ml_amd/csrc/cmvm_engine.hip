@@ -6,6 +6,7 @@
 // Reference loops replaced:
 //   k_prepare        _center + global digit width            bit_decompose.hh:25-34, bit_decompose.cc:22-27
 //   k_init_cells     CSD recoding + SparseExpr build          bit_decompose.cc:28-42, state_opr.cc:93-112
+//                    (the digits are digit_masks' of cmvm_core.h: the CSD form, or another minimal signed-digit form a chain asks for)
 //   k_init_pairs     all-pairs enumeration / FreqMap::initialize   state_opr.cc:117-143, types.hh:73-100
 //   k_iter_select2   idx_mc / idx_mc_dc / idx_wmc / idx_wmc_dc + update_expr   indexers.cc:6-90, state_opr.cc:227-283
 //                    (two workgroups per chain: the search finds the next pick one step AHEAD, beside the substitution of the current one;
@@ -886,10 +887,18 @@ __global__ void __launch_bounds__(256) k_init_state(ChainDev *chains) {
     fill16(ch.colbits, sizeof(uint32_t) * (size_t)ch.n_out * ch.cb_words, 0u, t0, stride);
 }
 
-template <class Cell> __global__ void __launch_bounds__(256) k_init_cells(ChainDev *chains) {
+// `recode`: the digit recoding of every chain of the launch (digit_masks, cmvm_core.h), in the order of `chains`; nullptr: all CSD.  A side
+// array and not a field of ChainDev: the layout of the descriptor is code to every other kernel (DESIGN.md sections 4a, 4b, 4c).
+struct ChainRecode {
+    unsigned long long seed;
+    uint32_t mode, pad;
+};
+template <class Cell> __global__ void __launch_bounds__(256) k_init_cells(ChainDev *chains, const ChainRecode *recode) {
     using O = CellOps<Cell>;
     using F = RowFmt<Cell>;
     ChainDev &ch = chains[blockIdx.y];
+    const uint32_t rc_mode = recode ? recode[blockIdx.y].mode : RECODE_CSD;
+    const uint64_t rc_seed = recode ? recode[blockIdx.y].seed : 0;
     int j = blockIdx.x * (blockDim.x / WAVE) + wave_id();
     if (j >= ch.n_out) return;
     auto *rl = reinterpret_cast<typename F::Entry *>(ch.rlist);
@@ -900,7 +909,7 @@ template <class Cell> __global__ void __launch_bounds__(256) k_init_cells(ChainD
         if (i < ch.n_in) {
             bool dead = ch.qints[3 * i] == 0.0f && ch.qints[3 * i + 1] == 0.0f;
             uint32_t p, m;
-            naf_masks(ch.xint[(size_t)i * ch.pn_out + ch.col0 + j], p, m);
+            digit_masks(ch.xint[(size_t)i * ch.pn_out + ch.col0 + j], rc_mode, rc_seed, p, m);
             c = dead ? (Cell)0 : O::make(p, m);
             rl[(size_t)i * ch.n_out + j] = F::pack((uint32_t)j, c);  // dense row: entry j is column j, empty cells included
         }

@@ -328,7 +328,13 @@ static bool host_chain(const ChainJob &job, ChainOut &out) {
             const int32_t x = (int32_t)a[(size_t)i * n_out + j];
             if (dead[i] || x == 0) continue;
             uint32_t p, m;
-            naf_masks(x, p, m);
+            digit_masks(x, job.recode, job.recode_seed, p, m);
+            if (job.method != M_DUMMY) {
+                // a chain without a greedy loop has at most one digit per column, so no cell has the two digits a rewrite site needs
+                uint32_t p0, m0;
+                naf_masks(x, p0, m0);
+                if (p != p0 || m != m0) throw std::logic_error("host_chain: a recoding rewrote the single digit of a column");
+            }
             out.dig_row.push_back((uint32_t)i);
             out.dig_cell.push_back((uint64_t)p | ((uint64_t)m << 32));
         }
@@ -726,7 +732,7 @@ std::vector<PipeResult> solve_batch_unique(Backend &be, const std::vector<Proble
 bool same_problem(const Problem &a, const Problem &b) {
     const SolveOptions &x = a.opt, &y = b.opt;
     if (a.n_in != b.n_in || a.n_out != b.n_out || x.hard_dc != y.hard_dc || x.decompose_dc != y.decompose_dc || x.adder_size != y.adder_size ||
-        x.carry_size != y.carry_size || x.search_all != y.search_all || x.seed != y.seed || x.tie_order != y.tie_order || f2u(x.dc_weight) != f2u(y.dc_weight) || x.method0 != y.method0 || x.method1 != y.method1 ||
+        x.carry_size != y.carry_size || x.search_all != y.search_all || x.seed != y.seed || x.tie_order != y.tie_order || x.recode != y.recode || x.recode_seed != y.recode_seed || f2u(x.dc_weight) != f2u(y.dc_weight) || x.method0 != y.method0 || x.method1 != y.method1 ||
         x.qints.size() != y.qints.size() || x.lats.size() != y.lats.size())
         return false;
     // bitwise comparisons: anything that is not literally the same input is simply solved again
@@ -767,7 +773,7 @@ uint64_t problem_hash(const Problem &p) {
     mix(p.kernel, sizeof(float) * (size_t)p.n_in * p.n_out);
     if (!p.opt.qints.empty()) mix(p.opt.qints.data(), sizeof(QInt) * p.opt.qints.size());
     if (!p.opt.lats.empty()) mix(p.opt.lats.data(), sizeof(float) * p.opt.lats.size());
-    const uint32_t seed_words[3] = {(uint32_t)p.opt.seed, (uint32_t)(p.opt.seed >> 32), p.opt.tie_order};
+    const uint32_t seed_words[6] = {(uint32_t)p.opt.seed, (uint32_t)(p.opt.seed >> 32), p.opt.tie_order, p.opt.recode, (uint32_t)p.opt.recode_seed, (uint32_t)(p.opt.recode_seed >> 32)};
     mix(seed_words, sizeof seed_words);  // (the restarts of one matrix differ in nothing else)
     const uint32_t weight_bits = f2u(p.opt.dc_weight);
     mix(&weight_bits, sizeof weight_bits);  // (nor do the points of a weight sweep)
@@ -916,8 +922,8 @@ std::vector<PipeResult> solve_batch_unique(Backend &be, const std::vector<Proble
                     c.allowed = c.hard_dc + s.minlat;
                     c.phase = Candidate::NEED_STAGE0;
                 } else if (!minlat_queued[c.problem]) {
-                    // minimal_latency(): adder trees straight from the CSD digits (api.cc:11-26); no greedy loop, so no tie seed
-                    jobs.push_back(ChainJob{p.kernel, p.n_in, p.n_out, M_DUMMY, s.qints.data(), s.lats.data(), p.opt.adder_size, p.opt.carry_size});
+                    // minimal_latency(): adder trees straight from the digits the problem's chains start from (api.cc:11-26); no greedy loop, so no tie seed
+                    jobs.push_back(ChainJob{p.kernel, p.n_in, p.n_out, M_DUMMY, s.qints.data(), s.lats.data(), p.opt.adder_size, p.opt.carry_size, 0, -1.0f, TIE_ORDER_RANDOM, p.opt.recode, p.opt.recode_seed});
                     owners.push_back(Pending{(int)ci, 0, c.problem});
                     minlat_queued[c.problem] = 1;
                     continue;
@@ -925,10 +931,10 @@ std::vector<PipeResult> solve_batch_unique(Backend &be, const std::vector<Proble
                     continue;
             }
             if (c.phase == Candidate::NEED_STAGE0) {
-                jobs.push_back(ChainJob{c.m0.data(), p.n_in, p.n_out, parse_method(c.method0), s.qints.data(), s.lats.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed, p.opt.dc_weight, p.opt.tie_order});
+                jobs.push_back(ChainJob{c.m0.data(), p.n_in, p.n_out, parse_method(c.method0), s.qints.data(), s.lats.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed, p.opt.dc_weight, p.opt.tie_order, p.opt.recode, p.opt.recode_seed});
                 owners.push_back(Pending{(int)ci, 1, c.problem});
             } else if (c.phase == Candidate::NEED_STAGE1) {
-                jobs.push_back(ChainJob{c.m1.data(), p.n_out, p.n_out, parse_method(c.method1), c.q_mid.data(), c.lat_mid.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed, p.opt.dc_weight, p.opt.tie_order});
+                jobs.push_back(ChainJob{c.m1.data(), p.n_out, p.n_out, parse_method(c.method1), c.q_mid.data(), c.lat_mid.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed, p.opt.dc_weight, p.opt.tie_order, p.opt.recode, p.opt.recode_seed});
                 owners.push_back(Pending{(int)ci, 2, c.problem});
             }
         }

@@ -55,6 +55,8 @@ struct ChainJob {
     uint64_t tie_seed = 0;  // 0: equal scores are settled as the reference settles them; else by the seeded tie order of cmvm_core.h (a random restart of the greedy search)
     float dc_weight = -1.0f;  // latency-penalty weight of a -dc / -pdc method (entry_rank, cmvm_core.h): finite and >= 0, or negative: the method's own constant.  Other methods ignore it; column-sharded chains keep the constant
     uint32_t tie_order = TIE_ORDER_RANDOM;  // which seeded order a chain with tie_seed != 0 runs (TIE_ORDER_*, cmvm_core.h); means nothing with tie_seed == 0
+    uint32_t recode = RECODE_CSD;  // the signed-digit form the chain starts from (RECODE_*, digit_masks of cmvm_core.h); column-sharded chains take RECODE_CSD only
+    uint64_t recode_seed = 0;  // the coin of RECODE_SEEDED; 0 under the other modes
 };
 struct ChainOut {
     int error = E_OK;
@@ -95,6 +97,9 @@ struct SolveOptions {
     uint64_t seed = 0;  // tie seed of every greedy chain of the problem (0: the reference's result)
     float dc_weight = -1.0f;  // latency-penalty weight of every greedy chain of the problem whose method is mc-dc, mc-pdc, wmc-dc or wmc-pdc; negative: unset, the reference's constant per method
     uint32_t tie_order = TIE_ORDER_RANDOM;  // seeded tie order of every greedy chain of the problem (TIE_ORDER_*); with seed 0 it is normalised to RANDOM: seed 0 is the reference whatever the order says
+    uint32_t recode = RECODE_CSD;  // digit recoding of every chain of the problem (RECODE_*): both stages, every decompose_dc candidate, every latency retry, and the
+                                   // adder trees the minimal latency is taken from.  The stage-1 distances count digits, which no mode changes: Stage1 stays shared
+    uint64_t recode_seed = 0;  // coin of RECODE_SEEDED; normalised to 0 under CSD and COMPACT, which do not read it: one problem to the de-duplication
 };
 
 int parse_method(const std::string &name);  // da::Method or -1

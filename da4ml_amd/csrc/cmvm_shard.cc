@@ -12,6 +12,8 @@ void ShardedBackend::run_chains(const ChainJob *jobs, ChainOut *outs, int n) {
     for (int i = 0; i < n; ++i) {
         const ChainJob &j = jobs[i];
         const bool shardable = (comm_.world > 1 || force_single) && j.n_out >= comm_.world && j.method >= 0 && j.method != M_DUMMY;
+        // the same answer on every rank, before any exchange: the job is the same everywhere
+        if (shardable && j.recode != RECODE_CSD) throw std::invalid_argument("column-sharded chains start from the CSD digits: no other recoding");
         if (shardable)
             run_one(j, outs[i]);
         else

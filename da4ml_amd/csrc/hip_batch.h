@@ -22,6 +22,7 @@ struct HipBackend::Impl::Batch {
     // set-up stream has been synchronised at the end of init_chains
     std::vector<StepLog2Host> step_tabs;
     std::vector<GatherPiece> pieces;
+    std::vector<ChainRecode> recode;  // the digit recoding of every chain, in the order of the device's descriptors: k_init_cells' side array
 
     ChainDev *d_desc = nullptr;
     int max_n_out = 0;
@@ -126,6 +127,17 @@ struct HipBackend::Impl::Batch {
             HIP_CHECK(hipMemcpyAsync(d_desc, sorted.data(), sizeof(ChainDev) * (size_t)n, hipMemcpyHostToDevice, st));
             HIP_CHECK(hipStreamSynchronize(st));
         }
+        // the recoding of every chain beside its descriptor, not in it (k_init_cells alone reads it); a batch of CSD chains passes none
+        const ChainRecode *d_recode = nullptr;
+        bool recoded = false;
+        for (int i = 0; i < n; ++i) recoded |= jobs[i].recode != RECODE_CSD;
+        if (recoded) {
+            recode.resize(n);
+            for (int s = 0; s < n; ++s) recode[s] = ChainRecode{jobs[order[s]].recode == RECODE_SEEDED ? jobs[order[s]].recode_seed : 0ull, jobs[order[s]].recode, 0u};
+            ChainRecode *buf = static_cast<ChainRecode *>(im.recode_buf.get(sizeof(ChainRecode) * (size_t)n));
+            HIP_CHECK(hipMemcpyAsync(buf, recode.data(), sizeof(ChainRecode) * (size_t)n, hipMemcpyHostToDevice, st));
+            d_recode = buf;
+        }
         int n_of[N_VAR] = {};
         for (int i = 0; i < n; ++i) ++n_of[variant(i)];
         for (int v = 0, first = 0; v < N_VAR; first += n_of[v], ++v) ranges[v] = Range{first, n_of[v], (v & 2) != 0, (v & 1) != 0, (v & 4) != 0, (v & 8) != 0};
@@ -151,7 +163,7 @@ struct HipBackend::Impl::Batch {
             ChainDev *base = d_desc + r.first;
             const dim3 colgrid((max_n_out + 3) / 4, r.count), pairgrid((unsigned)((max_pairs[w] + 3) / 4), r.count);
             with_cell(r.wide, [&](auto c) {
-                hipLaunchKernelGGL(k_init_cells<decltype(c)>, colgrid, dim3(256), 0, st, base);
+                hipLaunchKernelGGL(k_init_cells<decltype(c)>, colgrid, dim3(256), 0, st, base, d_recode ? d_recode + r.first : nullptr);
                 with_flag(r.seeded, [&](auto sd) {
                     with_flag(r.weighted, [&](auto wt) { hipLaunchKernelGGL((k_init_pairs<decltype(c), decltype(sd)::value, decltype(wt)::value>), pairgrid, dim3(256), pair_lds[w], st, base); });
                 });

@@ -17,7 +17,7 @@ struct HipBackend::Impl {
     int upd_total_blocks = 2560;  // k_iter_update blocks over all chains of a batch (4 waves x 4 groups each); measured (C3 batch 64,
                                   // solves/s): 1024: 45.3, 1536: 53.3, 2048: 53.8, 2560: 55.5, 4096: 47.5; again with seven resident waves per SIMD
                                   // (profiles/ab_update_register_diet.txt): 1792: 110.9, 2048: 112.8, 2304: 113.4, 2560: 113.2 - 113.7, 3072: 113.7, 3328: 113.0 -- flat around 2560
-    DeviceBuffer arena, desc_buf, io_buf, gather_buf, piece_buf;  // gather_buf: the results of a batch, contiguous, before they leave
+    DeviceBuffer arena, desc_buf, io_buf, gather_buf, piece_buf, recode_buf;  // gather_buf: the results of a batch, contiguous, before they leave; recode_buf: k_init_cells' side array
     unsigned int *d_done = nullptr;
     unsigned int *h_done = nullptr;  // pinned, two words: done counters of alternating poll windows
     hipStream_t poll_stream = nullptr;

@@ -65,7 +65,7 @@ class HipShardEngine : public ShardEngine {
         for (int q = 0; q < 5; ++q) report_[q] = 0;
         d_done_ = static_cast<unsigned int *>(done_buf_.get(sizeof(unsigned int)));  // (a member buffer: released also when a later check of this constructor throws)
         HIP_CHECK(hipMemsetAsync(d_done_, 0, sizeof(unsigned int), st_));
-        per_cell([&](auto c) { hipLaunchKernelGGL(k_init_cells<decltype(c)>, dim3((n_loc_ + 3) / 4, 1), dim3(256), 0, st_, dd_); });
+        per_cell([&](auto c) { hipLaunchKernelGGL(k_init_cells<decltype(c)>, dim3((n_loc_ + 3) / 4, 1), dim3(256), 0, st_, dd_, (const ChainRecode *)nullptr); });
         HIP_CHECK(hipGetLastError());
         sel_lds_ = align_up(sel2_fixed_lds(n_loc_, g) + (size_t)d_.claim_words * 4, 16);
         if (sel_lds_ > sel2_lds_budget(device_, g.wide)) throw std::runtime_error("selection kernel needs more dynamic LDS than the device leaves beside its static arrays (n_out too large)");

@@ -300,23 +300,27 @@ def solve_candidates_sharded(kernel, method0: str = 'wmc', method1: str = 'auto'
     return box[0]
 
 
-def solve_restarts_sharded(kernel, n_restarts: int, seed: int = 0, solver=None, order: str = 'random', **opts):
+def solve_restarts_sharded(kernel, n_restarts: int, seed: int = 0, solver=None, order: str = 'random', recode: str = 'csd', **opts):
     """``da4ml_amd.cmvm.solve_restarts`` with the restarts sharded over the ranks: restart ``r`` (tie seed
     ``cmvm.restart_seeds(n_restarts, seed)[r]``) runs on rank ``r % world``, each rank's restarts in one call on its own GPU.
     The shape of ``solve_candidates_sharded``: one all-reduce(MIN) over the cost vector, the first-strict-minimum rule, a
     broadcast of the winning Pipeline from the rank that owns it.  Every rank returns the same Pipeline, identical to the
     one-process ``solve_restarts``.  ``solver(kernels, seeds=..., **opts)`` defaults to the HIP path (``_binary.solve_many``);
     the CPU tests inject a stand-in.  ``order``: ``'random'`` or ``'newest'`` as for ``solve_restarts``; another order than the default reaches
-    the solver as ``tie_order=``."""
+    the solver as ``tie_order=``.  ``recode``: ``'csd'``, ``'compact'`` or ``'seeded'`` as for ``solve_restarts``; another recoding than the
+    default reaches the solver as ``recode=``."""
     import torch
     import torch.distributed as dist
 
-    from ._binary import tie_order_code
+    from ._binary import recode_code, tie_order_code
     from .cmvm import first_strict_minimum, restart_seeds
 
     tie_order_code(order)
     if order != 'random':
         opts = {**opts, 'tie_order': order}
+    recode_code(recode)
+    if recode != 'csd':
+        opts = {**opts, 'recode': recode}
 
     rank, world, local, device = init()
     if solver is None:

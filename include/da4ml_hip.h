@@ -133,6 +133,34 @@ typedef struct da_solve_opts {
 int da_solve_batch_opts(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const da_solve_opts *opts /* [count] */,
                         const float *const *qintervals, const float *const *latencies, da_result **results);
 
+/* da_solve_batch_opts with a digit recoding per problem (addition, no reference counterpart).  Every greedy chain starts from the CSD
+ * (non-adjacent form) digits of its matrix, as the reference does.  The NAF is one of several minimal signed-digit forms of a number
+ * (3 = 4 - 1 = 2 + 1); which form the search starts from changes which digit pairs repeat, and with them the adder count.
+ *   DA_RECODE_CSD      the NAF: the reference's digits.
+ *   DA_RECODE_COMPACT  the NAF digits d scanned from (top position - 2) down to 0: a site d[p+2] = s != 0, d[p+1] = 0, d[p] = -s becomes
+ *                      d[p+2] = 0, d[p+1] = s, d[p] = s (11 = 16 - 4 - 1 -> 8 + 4 - 1 -> 8 + 2 + 1).
+ *   DA_RECODE_SEEDED   the same scan; a site is rewritten only when a coin keyed by (seed, |value|, p) says so.  Equal values get equal
+ *                      digits wherever they stand, x and -x mirrored ones.
+ * Every mode keeps the value, the digit count and the top position of every entry.  The mode goes into every chain of the problem: both
+ * stages, every decompose_dc candidate, every latency retry, and the adder trees the minimal latency of hard_dc is measured on.
+ * da_solve_opts cannot grow any further (its size is pinned), hence the second array.
+ * Contract: recode == NULL, or mode DA_RECODE_CSD, is da_solve_batch_opts bit for bit; a mode other than the three, or a struct_size
+ * other than sizeof(da_recode_opts), gives DA_ERR_VALUE; seed is read under DA_RECODE_SEEDED only; the result of a problem depends on
+ * nothing but its own matrix and options, whatever else the batch holds and wherever it stands in it; the same inputs give the same
+ * result on every run.  Compact digits save 1 to 3 % of the adders at 3 to 5 bit weights and lose at 8 bits: a restart dimension
+ * (da4ml_amd.cmvm.solve_recoded), never a default.  Column-sharded chains start from the CSD digits only. */
+#define DA_RECODE_CSD 0u
+#define DA_RECODE_COMPACT 1u
+#define DA_RECODE_SEEDED 2u
+typedef struct {
+    uint32_t struct_size;
+    uint32_t mode;
+    uint64_t seed;
+} da_recode_opts;
+int da_solve_batch_recode(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const da_solve_opts *opts /* [count] */,
+                          const da_recode_opts *recode /* [count] or NULL */, const float *const *qintervals, const float *const *latencies,
+                          da_result **results);
+
 /* ---- column-sharded solve (BASELINE config C4; addition, no reference counterpart) ------------------------------------------
  * da_solve with every greedy chain sharded over the output COLUMNS of its matrix across `world` processes (one per GPU):
  * rank g holds the digits of columns [g n_out / world, (g+1) n_out / world), the pair-count table is replicated, and per
