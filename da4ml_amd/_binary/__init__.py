@@ -27,7 +27,7 @@ _i32p = np.ctypeslib.ndpointer(np.int32, flags='C_CONTIGUOUS')
 
 EXPORTS = (
     'da_last_error da_last_error_code da_version da_device_count da_set_device da_get_lsb_loc da_iceil_log2 da_cost_add da_int_arr_to_csd '
-    'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_batch_seeded da_solve_batch_opts da_solve_batch_recode da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
+    'da_csd_decompose da_kernel_decompose da_solve da_solve_batch da_solve_batch_seeded da_solve_batch_opts da_solve_batch_recode da_solve_batch_search da_solve_sharded da_rccl_unique_id da_rccl_shutdown da_solve_sharded_rccl da_comm_abort da_shard_exchanged_elements da_n_stages da_picked da_stage_info da_stage_copy '
     'da_result_stats da_free da_timings da_engine_stats da_dais_run da_dais_last_error da_dais_run_on '
     'da_dais_compile da_dais_exec_info da_dais_exec_scratch da_dais_exec_run da_dais_exec_free '
     'da_dais_exec_run_mode da_dais_exec_info2 da_dais_exec_level_schedule'
@@ -93,6 +93,8 @@ def lib():
         L.da_solve_batch_opts.argtypes = [C.c_int, C.c_void_p, _i64p, _i64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, 'da_solve_batch_recode'):  # (likewise)
         L.da_solve_batch_recode.argtypes = [C.c_int, C.c_void_p, _i64p, _i64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, 'da_solve_batch_search'):  # (likewise)
+        L.da_solve_batch_search.argtypes = [C.c_int, C.c_void_p, _i64p, _i64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.da_solve_sharded.restype = C.c_void_p
     L.da_solve_sharded.argtypes = [_f32p, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, _i64p]  # fmt: skip
@@ -338,6 +340,7 @@ def solve_many(
     seeds=None,
     tie_order='random',
     recode='csd',
+    slack=0,
 ):
     """Solve independent matrices concurrently on the GPU (addition to the reference API; same options as ``solve``).
 
@@ -355,14 +358,18 @@ def solve_many(
     ``recode``: the signed-digit form the chains of a problem with a seed other than 0 start from -- ``'csd'`` (the default: the
     reference's digits), ``'compact'`` or ``'seeded'`` (the coin's seed is the problem's tie seed), see ``solve_each``; one name for the
     whole batch.  A problem with seed 0 stays the reference's result.
+
+    ``slack``: the score slack of the problems with a seed other than 0 -- an int 0 .. 255 (0, the default: none), see ``solve_each``; one
+    value for the whole batch.  A problem with seed 0 stays the reference's result.
     """
     order = tie_order_code(tie_order)
     recoded = recode_code(recode) != RECODES['csd']
+    slack = slack_value(slack)
     ks = [_kernel(k) for k in kernels]
     n = len(ks)
     if n == 0:
         return []
-    if order != TIE_ORDERS['random'] or recoded:  # (da_solve_batch_seeded stays the random order and the CSD digits: the rest goes through the per-problem structs)
+    if order != TIE_ORDERS['random'] or recoded or slack:  # (da_solve_batch_seeded stays the random order, the CSD digits and the reference's scores: the rest goes through the per-problem structs)
         if seeds is None:
             seeds = [0] * n
         if len(seeds) != n:
@@ -370,6 +377,8 @@ def solve_many(
         shared = dict(method0=method0, method1=method1, hard_dc=hard_dc, decompose_dc=decompose_dc, adder_size=adder_size, carry_size=carry_size,
                       search_all_decompose_dc=search_all_decompose_dc, tie_order=tie_order)  # fmt: skip
         each = [dict(shared, seed=s, recode=recode, recode_seed=s) if recoded and int(s) else dict(shared, seed=s) for s in seeds]
+        if slack:
+            each = [dict(o, slack=slack) if int(s) else o for o, s in zip(each, seeds)]
         return solve_each(ks, each, qintervals=qintervals, latencies=latencies, _stats=_stats)
     seed_arr = None
     if seeds is not None:
@@ -423,6 +432,19 @@ def recode_code(name) -> int:
     return RECODES[name]
 
 
+def slack_value(slack) -> int:
+    """A score slack as ``da_search_opts`` takes it: an int 0 .. 255; anything else is a ``ValueError``"""
+    if isinstance(slack, bool) or not isinstance(slack, (int, np.integer)) or not 0 <= int(slack) <= 255:
+        raise ValueError(f'slack must be an int in 0 .. 255, not {slack!r}')
+    return int(slack)
+
+
+class SearchOpts(C.Structure):
+    """``da_search_opts`` (include/da4ml_hip.h): the score slack of one problem of ``da_solve_batch_search``"""
+
+    _fields_ = [('struct_size', C.c_uint32), ('slack', C.c_uint32)]
+
+
 class RecodeOpts(C.Structure):
     """``da_recode_opts`` (include/da4ml_hip.h): the digit recoding of one problem of ``da_solve_batch_recode``"""
 
@@ -447,7 +469,7 @@ class SolveOpts(C.Structure):
     ]
 
 
-_EACH_DEFAULTS = dict(method0='wmc', method1='auto', hard_dc=-1, decompose_dc=-2, adder_size=-1, carry_size=-1, search_all_decompose_dc=True, seed=0, dc_weight=None, tie_order='random', recode='csd', recode_seed=0)
+_EACH_DEFAULTS = dict(method0='wmc', method1='auto', hard_dc=-1, decompose_dc=-2, adder_size=-1, carry_size=-1, search_all_decompose_dc=True, seed=0, dc_weight=None, tie_order='random', recode='csd', recode_seed=0, slack=0)
 
 
 def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool = False):
@@ -458,7 +480,10 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
     weight of the ``*-dc`` / ``*-pdc`` selectors: a finite number >= 0, or ``None``: the reference's constant per method) and ``tie_order``
     (``'random'`` or ``'newest'``: the order a seed other than 0 gives, see ``solve_many``; anything else is a ``ValueError``), and ``recode``
     / ``recode_seed``: the signed-digit form the problem's chains start from -- ``'csd'`` (the reference's), ``'compact'`` or ``'seeded'``
-    with the coin's seed (``da_solve_batch_recode``; ``da4ml_amd.cmvm.solve_recoded`` is the user-facing entry).  Missing keys
+    with the coin's seed (``da_solve_batch_recode``; ``da4ml_amd.cmvm.solve_recoded`` is the user-facing entry), and ``slack``: an int
+    0 .. 255 (anything else is a ``ValueError``), 0: none -- the problem's greedy chains discount the score of every pair by at most
+    slack / 256 of it, a hash of (pair, seed), so that near-best pairs win some steps (``da_solve_batch_search``; it wants ``seed`` != 0;
+    ``da4ml_amd.cmvm.solve_restarts(..., slack=)`` is the user-facing entry).  Missing keys
     have ``solve``'s defaults.  ``qintervals`` / ``latencies`` as for ``solve_many``.  The result of a problem depends on nothing but its
     own matrix and options.  ``da4ml_amd.cmvm.solve_tradeoff`` is the user-facing entry for weight sweeps."""
     ks = [_kernel(k) for k in kernels]
@@ -471,6 +496,7 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
         raise RuntimeError(f'{_LIB_PATH} has no da_solve_batch_opts: per-problem options need the library of this revision')
     opts = (SolveOpts * n)()
     recode = (RecodeOpts * n)()
+    search = (SearchOpts * n)()
     for i, given in enumerate(options):
         unknown = set(given) - set(_EACH_DEFAULTS)
         if unknown:
@@ -482,6 +508,7 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
         opts[i] = SolveOpts(C.sizeof(SolveOpts), o['method0'].encode(), o['method1'].encode(), int(o['hard_dc']), int(o['decompose_dc']), int(o['adder_size']),
                             int(o['carry_size']), int(bool(o['search_all_decompose_dc'])), w, int(o['seed']) & 0xFFFFFFFFFFFFFFFF, tie_order_code(o['tie_order']))  # fmt: skip
         recode[i] = RecodeOpts(C.sizeof(RecodeOpts), recode_code(o['recode']), int(o['recode_seed']) & 0xFFFFFFFFFFFFFFFF)
+        search[i] = SearchOpts(C.sizeof(SearchOpts), slack_value(o['slack']))
     n_in = np.array([k.shape[0] for k in ks], np.int64)
     n_out = np.array([k.shape[1] for k in ks], np.int64)
     kptr = (C.c_void_p * n)(*[k.ctypes.data for k in ks])
@@ -495,7 +522,11 @@ def solve_each(kernels, options, qintervals=None, latencies=None, _stats: bool =
             ls.append(None if l is None else l.ctypes.data)
         qptr, lptr = (C.c_void_p * n)(*qs), (C.c_void_p * n)(*ls)
     res = (C.c_void_p * n)()
-    if all(r.mode == RECODES['csd'] for r in recode):  # (the call every batch made before there were recodings)
+    if any(s.slack for s in search):
+        if not hasattr(lib(), 'da_solve_batch_search'):
+            raise RuntimeError(f'{_LIB_PATH} has no da_solve_batch_search: a score slack needs the library of this revision')
+        rc = lib().da_solve_batch_search(n, kptr, n_in, n_out, C.cast(opts, C.c_void_p), C.cast(recode, C.c_void_p), C.cast(search, C.c_void_p), qptr, lptr, res)
+    elif all(r.mode == RECODES['csd'] for r in recode):  # (the call every batch made before there were recodings)
         rc = lib().da_solve_batch_opts(n, kptr, n_in, n_out, C.cast(opts, C.c_void_p), qptr, lptr, res)
     else:
         if not hasattr(lib(), 'da_solve_batch_recode'):

@@ -5,7 +5,7 @@ from typing import NamedTuple, TypedDict
 
 import numpy as np
 
-from .._binary import kernel_decompose, recode_code, solve, solve_each, solve_many, tie_order_code
+from .._binary import kernel_decompose, recode_code, slack_value, solve, solve_each, solve_many, tie_order_code
 from ..types import CombLogic, Op, QInterval
 
 
@@ -48,7 +48,7 @@ def first_strict_minimum(costs) -> int:
     return best
 
 
-def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = False, order: str = 'random', recode: str = 'csd', **solve_options):
+def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = False, order: str = 'random', recode: str = 'csd', slack: int = 0, **solve_options):
     """Best of ``n_restarts`` greedy searches of one matrix (addition to the reference API; ``solve_options`` as for ``solve``).
 
     Most greedy steps have several equally scored pairs, and the reference takes the last of them in its sorted table.
@@ -68,16 +68,24 @@ def solve_restarts(kernel, n_restarts: int, seed: int = 0, return_all: bool = Fa
     as every restart had them so far.  ``'compact'``: the compact digits.  ``'seeded'``: the restart's own seed also draws the coins of
     its digits.  Restart 0 stays ``solve``.  Anything else is a ``ValueError``.
 
+    ``slack``: an int 0 .. 255 (anything else is a ``ValueError``); 0, the default: none.  The restarts r >= 1 discount the score of every
+    pair by at most slack / 256 of it, a hash of (pair, key, the restart's seed): a pair whose score lies within that fraction of the best
+    can win the step -- the restricted candidate list of a randomised greedy search, where the tie orders move equally scored pairs only.
+    Restart 0 stays ``solve``, so the result is never dearer.  Small slacks (2 to 8) are the useful ones; 32 and more lose (README).
+
     ``return_all=True``: ``(best_index, [Pipeline, ...], [cost, ...])`` instead of the winning Pipeline."""
     from ..multi_gpu import pipeline_cost_f32
 
     tie_order_code(order)
     recode_code(recode)
+    slack = slack_value(slack)
     seeds = restart_seeds(n_restarts, seed)
     if order != 'random':
         solve_options = {**solve_options, 'tie_order': order}
     if recode != 'csd':
         solve_options = {**solve_options, 'recode': recode}
+    if slack:
+        solve_options = {**solve_options, 'slack': slack}
     per_kernel = {k: [v] * len(seeds) for k, v in solve_options.items() if k in ('qintervals', 'latencies') and v is not None}
     opts = {k: v for k, v in solve_options.items() if k not in ('qintervals', 'latencies')}
     pipes = solve_many([kernel] * len(seeds), seeds=seeds, **opts, **per_kernel)
@@ -104,7 +112,7 @@ def solve_recoded(kernel, n: int = 8, seed: int = 0, return_all: bool = False, *
     ``return_all=True``: ``(best_index, [Pipeline, ...], [cost, ...])`` instead of the winning Pipeline."""
     from ..multi_gpu import pipeline_cost_f32
 
-    for key in ('seed', 'tie_order', 'dc_weight', 'recode', 'recode_seed'):  # (solve takes none of them: point 0 would no longer be solve(kernel, **solve_options))
+    for key in ('seed', 'tie_order', 'dc_weight', 'recode', 'recode_seed', 'slack'):  # (solve takes none of them: point 0 would no longer be solve(kernel, **solve_options))
         if key in solve_options:
             raise TypeError(f"solve_recoded() takes solve's keywords: {key!r} is not one of them")
     seeds = restart_seeds(n, seed)

@@ -183,6 +183,12 @@ int da_solve_batch_opts(int count, const float *const *kernels, const int64_t *n
 
 int da_solve_batch_recode(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const da_solve_opts *opts,
                           const da_recode_opts *recode, const float *const *qintervals, const float *const *latencies, da_result **results) {
+    return da_solve_batch_search(count, kernels, n_in, n_out, opts, recode, nullptr, qintervals, latencies, results);
+}
+
+int da_solve_batch_search(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const da_solve_opts *opts,
+                          const da_recode_opts *recode, const da_search_opts *search, const float *const *qintervals, const float *const *latencies,
+                          da_result **results) {
     std::lock_guard<LibraryMutex> lk(g_mutex);
     try {
         if (count > 0 && !opts) throw std::invalid_argument("opts must hold one da_solve_opts per problem");
@@ -190,6 +196,10 @@ int da_solve_batch_recode(int count, const float *const *kernels, const int64_t 
         for (int i = 0; recode && i < count; ++i) {
             if (recode[i].struct_size != sizeof(da_recode_opts)) throw std::invalid_argument("recode[" + std::to_string(i) + "].struct_size is not sizeof(da_recode_opts)");
             if (recode[i].mode >= da::RECODE_COUNT) throw std::invalid_argument("recode mode must be DA_RECODE_CSD, DA_RECODE_COMPACT or DA_RECODE_SEEDED");
+        }
+        for (int i = 0; search && i < count; ++i) {
+            if (search[i].struct_size != sizeof(da_search_opts)) throw std::invalid_argument("search[" + std::to_string(i) + "].struct_size is not sizeof(da_search_opts)");
+            if (search[i].slack > 255u) throw std::invalid_argument("slack must lie in 0 .. 255");
         }
         std::vector<da::Problem> probs((size_t)count);
         for (int i = 0; i < count; ++i) {
@@ -228,6 +238,8 @@ int da_solve_batch_recode(int count, const float *const *kernels, const int64_t 
             p.opt.dc_weight = o.dc_weight == DA_DC_WEIGHT_DEFAULT ? -1.0f : o.dc_weight + 0.0f;  // (+ 0: -0 and 0 are one weight)
             p.opt.recode = recode ? recode[i].mode : (uint32_t)DA_RECODE_CSD;
             p.opt.recode_seed = p.opt.recode == da::RECODE_SEEDED ? recode[i].seed : 0;  // (CSD and COMPACT read no seed: one problem to the de-duplication)
+            p.opt.slack = search ? search[i].slack : 0u;
+            if (p.opt.slack && !o.seed) throw std::invalid_argument("a slack is keyed by the problem's seed: slack != 0 wants seed != 0");
         }
         std::vector<da::ChainStats> stats;
         const auto t0 = std::chrono::steady_clock::now();
@@ -363,6 +375,7 @@ static da_result *solve_sharded_impl(const float *kernel, int64_t n_in, int64_t 
         p.opt.carry_size = carry_size;
         p.opt.search_all = search_all_decompose_dc != 0;
         if (const char *e = std::getenv("DA4ML_SHARD_RECODE")) p.opt.recode = (uint32_t)std::atoi(e);  // test hook: the sharded entry points take no recoding, and a column-sharded chain refuses one
+        if (const char *e = std::getenv("DA4ML_SHARD_SLACK")) p.opt.slack = (uint32_t)std::atoi(e);  // test hook: ... nor a slack
         da::gpu::HipBackend &inner = backend();
         da::ShardComm comm;
         comm.rank = rank;

@@ -349,6 +349,72 @@ DA_HD uint32_t entry_rank(uint32_t count, int ov, float dl, int method, float w)
 // the reference's scores: every method with its own constant
 DA_HD uint32_t entry_rank(uint32_t count, int ov, float dl, int method) { return detail::entry_rank_weights(count, ov, dl, method, DC_WEIGHT_MC, DC_WEIGHT_WMC); }
 
+// ------------------------------------------------------------------------------------ score slack
+// A chain with a slack != 0 (and a tie seed != 0: the slack is keyed by it) draws its pick from the pairs whose score lies within a small fraction
+// of the best one -- the restricted candidate list of a randomised greedy search.  No reference counterpart: a restart dimension, never a default.
+// Every entry gets a discount of its OWN, a pure function of (count, rows, key, the chain's constants): the table stays exact and incremental.
+//   slack_byte(id0, id1, idx, seed) in 0 .. 255: a keyed hash of the row pair and the key index, 32-bit arithmetic only.
+//       word = slack_pair_word(id0, id1, seed): the two ids and the two halves of the seed combined by four odd multipliers, then the "lowbias32"
+//              finaliser (h ^= h >> 16, h *= 0x7FEB352D, h ^= h >> 15, h *= 0x846CA68B, h ^= h >> 16); once per block (row pair);
+//       byte = ((word ^ idx * 0x9E3779) * 0x9E3779B1) >> 24: a 24-bit multiply, an xor, a multiply and a shift per key.  (The xor is what
+//              unties the keys of a block: with word * (2 idx + 1), or any form linear in the word, the byte of key 1 is a fixed function of
+//              the byte of key 0 in every block -- a correlation of 0.34 between the two over a grid of pairs.)
+//   entry_rank_slack(count, ov, dl, method, w, slack, byte), slack in 0 .. 255:
+//       base = count (mc family) | the integer product count * ov (wmc family: signed for wmc, the reference's unsigned wrap for wmc-dc / wmc-pdc);
+//       0 < base < 2^24:  base -= (base * ((byte * slack) >> 8)) >> 8      -- at most slack / 256 of the score; base * 254 < 2^32: no 64-bit multiply
+//       otherwise base is left alone (zero, negative, the unsigned wrap of a negative overlap, products the float would round anyway);
+//       then entry_rank's: mc / wmc rank = base + 1; the -dc / -pdc methods float(base) - w * dl with its two single roundings, the `absolute`
+//       cut, float_rank.  count < 2 is 0, as there.
+// Properties (tests/test_slack_rank.py): slack == 0 is entry_rank(count, ov, dl, method, w) bit for bit; the rank is non-decreasing in count
+// (b -> b - floor(b d / 256), d <= 254, never steps down, and 2^24 - 1 maps below 2^24); a discounted base >= 1 stays >= 1 (b d / 256 < b).
+// Entries of equal rank are ordered by the chain's tie word, unchanged.
+DA_HD uint32_t slack_pair_word(uint32_t id0, uint32_t id1, uint64_t seed) {
+    uint32_t h = id0 * 0x9E3779B1u + id1 * 0x85EBCA77u + (uint32_t)seed * 0xC2B2AE3Du + (uint32_t)(seed >> 32) * 0x27D4EB2Fu;
+    h ^= h >> 16;
+    h *= 0x7FEB352Du;
+    h ^= h >> 15;
+    h *= 0x846CA68Bu;
+    h ^= h >> 16;
+    return h;
+}
+DA_HD uint32_t slack_word_byte(uint32_t word, uint32_t idx) { return ((word ^ (idx * 0x9E3779u)) * 0x9E3779B1u) >> 24; }
+DA_HD uint32_t slack_byte(uint32_t id0, uint32_t id1, int idx, uint64_t seed) { return slack_word_byte(slack_pair_word(id0, id1, seed), (uint32_t)idx); }
+DA_HD uint32_t slack_discount(uint32_t base, uint32_t slack, uint32_t byte) {
+    return base - 1u < 0xFFFFFFu ? base - ((base * ((byte * slack) >> 8)) >> 8) : base;
+}
+DA_HD uint32_t entry_rank_slack(uint32_t count, int ov, float dl, int method, float w, uint32_t slack, uint32_t byte) {
+    if (count < 2) return 0;
+    switch (method) {
+    case M_MC: return slack_discount(count, slack, byte) + 1;
+    case M_WMC: {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (count <= 0xFFFFu) {  // (as entry_rank: the product fits 32 bits)
+            const int32_t s32 = (int32_t)count * ov;
+            return s32 >= 0 ? slack_discount((uint32_t)s32, slack, byte) + 1 : 0;
+        }
+#endif
+        int64_t s = (int64_t)count * ov;
+        return s >= 0 ? slack_discount((uint32_t)s, slack, byte) + 1 : 0;
+    }
+    case M_MC_DC:
+    case M_MC_PDC:
+    case M_WMC_DC:
+    case M_WMC_PDC: {
+        const bool mc = method == M_MC_DC || method == M_MC_PDC;
+        const uint32_t base = slack_discount(mc ? count : count * (uint32_t)ov, slack, byte);
+#if defined(__HIP_DEVICE_COMPILE__)
+        float s = __fsub_rn((float)base, __fmul_rn(w, dl));
+#else
+        float pen = w * dl;
+        float s = (float)base - pen;
+#endif
+        if ((method == M_MC_DC || method == M_WMC_DC) && !(s >= 0.0f)) return 0;
+        return float_rank(s);
+    }
+    default: return 0;
+    }
+}
+
 // tie-break word: larger == later in the reference's sorted table (id1, id0, sub, shift)
 DA_HD uint64_t tie_word(uint32_t id0, uint32_t id1, int idx) {
     return ((uint64_t)id1 << 31) | ((uint64_t)id0 << 7) | (uint64_t)idx;

@@ -381,6 +381,7 @@ struct ChainDev {
     float dc_weight;                  // latency-penalty weight of the -dc / -pdc methods (entry_rank, cmvm_core.h); the host always fills it, by default with the method's
                                       // constant.  Read by the WEIGHTED instantiations only: the others keep the constant as a literal (last field, as tie_seed was)
     uint32_t tie_order;               // which seeded tie order a chain with tie_seed != 0 runs (TIE_ORDER_*, cmvm_core.h).  Read by the SEEDED instantiations only (last field again)
+    uint32_t slack;                   // score slack of the chain (entry_rank_slack, cmvm_core.h), 0 .. 255; 0: none.  Read by the SLACK instantiations only (last field again)
 };
 
 __constant__ Log2Table c_log2;
@@ -528,14 +529,31 @@ template <bool WEIGHTED> __device__ __forceinline__ uint32_t rank_of(const Ctx &
 // ---- block evaluator: how the counts of a pair block become its best entry.  Every code path that writes a block's counts (table_insert, table_update,
 // and in update_partners the side-by-side re-evaluation and the block creation) forms its candidates, keeps the best and takes it apart HERE, so the
 // chain's rank (weight) and tie order (seed) are threaded through one place.  It carries what a rank needs: the chain context and the weight bits.
-template <bool SEEDED, bool WEIGHTED> struct BlockEval {
+// SLACK: the chain scores with a slack (entry_rank_slack, cmvm_core.h).  Such a chain always has a seed and reads its weight from the descriptor
+// (the host fills in the method's constant where the job sets none): the SLACK instantiations exist with SEEDED and WEIGHTED only.  A rank then
+// depends on the block's rows as well: `pw`, the per-block word of slack_pair_word, formed once per block by the code that walks its keys (0 and
+// dead code in the other instantiations, which are instruction for instruction what they were).
+template <bool SEEDED, bool WEIGHTED, bool SLACK = false> struct BlockEval {
+    static_assert(!SLACK || (SEEDED && WEIGHTED), "a slack chain has a seed and carries its weight");
     const Ctx &c;
     uint32_t dcw;  // bits of the chain's latency-penalty weight in the WEIGHTED instantiations, unused (0) in the others
     uint32_t ord;  // the chain's seeded tie order (TIE_ORDER_*) in the SEEDED instantiations, unused (0) in the others
-    // candidate word of key `k` with count `n` in a block of rows with overlap `ov`, latency difference `dl`: rank << 8 | position in the
-    // within-block order, 0 = not selectable
-    __device__ __forceinline__ unsigned long long candidate(uint32_t n, uint32_t k, int ov, float dl) const {
-        const uint32_t r = rank_of<WEIGHTED>(c, dcw, n, ov, dl);
+    uint32_t slk;  // the chain's score slack (1 .. 255) in the SLACK instantiations, unused (0) in the others
+    // the per-block word of the slack's hash for the block of rows lo <= hi
+    __device__ __forceinline__ uint32_t pair_word(uint32_t lo, uint32_t hi) const {
+        if constexpr (SLACK)
+            return slack_pair_word(lo, hi, c.seed);
+        else
+            return 0u;
+    }
+    // candidate word of key `k` with count `n` in a block of rows with overlap `ov`, latency difference `dl` and pair word `pw`: rank << 8 |
+    // position in the within-block order, 0 = not selectable
+    __device__ __forceinline__ unsigned long long candidate(uint32_t n, uint32_t k, int ov, float dl, uint32_t pw) const {
+        uint32_t r;
+        if constexpr (SLACK)
+            r = entry_rank_slack(n, ov, dl, c.method, u2f(dcw), slk, slack_word_byte(pw, k));
+        else
+            r = rank_of<WEIGHTED>(c, dcw, n, ov, dl);
         return r ? (((unsigned long long)r << 8) | blk_pos<SEEDED>(k, c.seed)) : 0ull;
     }
     static __device__ __forceinline__ void fold(unsigned long long &best, unsigned long long cand) { best = cand > best ? cand : best; }
@@ -675,8 +693,8 @@ __device__ __forceinline__ DA_GLOBAL uint8_t *hidx_ptr(const Ctx &c) { return re
 
 // one lane: publish a block just created in `slot` (its counts are stored by the lanes that hold them) -- header, rank and best-key index, the
 // group's bound, the candidate list of the next pick.  `best`: the block's best candidate word
-template <bool SEEDED, bool WEIGHTED>
-__device__ __forceinline__ void publish_new_block(const BlockEval<SEEDED, WEIGHTED> &ev, int slot, uint32_t lo, uint32_t hi, int ov, float dl, unsigned long long best) {
+template <bool SEEDED, bool WEIGHTED, bool SLACK>
+__device__ __forceinline__ void publish_new_block(const BlockEval<SEEDED, WEIGHTED, SLACK> &ev, int slot, uint32_t lo, uint32_t hi, int ov, float dl, unsigned long long best) {
     const Ctx &c = ev.c;
     const uint32_t rank = ev.rank_of_best(best), idx = ev.idx_of_best(best);
     store_hdr(c, slot, ov, dl, rank, idx);
@@ -694,8 +712,8 @@ __device__ __forceinline__ void publish_new_block(const BlockEval<SEEDED, WEIGHT
 // ONCE PER WORKGROUP: in the first thousands of steps of a chain hundreds of blocks are created and deleted per step, and one atomic each on the
 // same line of the chain descriptor serialises in the L2 at ~12 ns apiece -- behind which every later load of the issuing wave waits (vmcnt is
 // in-order): measured in round 6, k_iter_update of steps 0 - 2000 took 24.8 us for one chain where the late steps take 6.7.
-template <bool SEEDED, bool WEIGHTED, class CntFn>
-__device__ bool table_insert(const BlockEval<SEEDED, WEIGHTED> &ev, uint32_t lo, uint32_t hi, const RowInfo &ra, const RowInfo &rb, CntFn cnt_of, bool tally = true) {
+template <bool SEEDED, bool WEIGHTED, bool SLACK, class CntFn>
+__device__ bool table_insert(const BlockEval<SEEDED, WEIGHTED, SLACK> &ev, uint32_t lo, uint32_t hi, const RowInfo &ra, const RowInfo &rb, CntFn cnt_of, bool tally = true) {
     const Ctx &c = ev.c;
     int lane = lane_id();
     unsigned long long key = pack_pair(lo, hi);
@@ -708,11 +726,12 @@ __device__ bool table_insert(const BlockEval<SEEDED, WEIGHTED> &ev, uint32_t lo,
     float dl = fabsf(ra.lat - rb.lat);
     unsigned long long best = 0;
     DA_GLOBAL uint16_t *cnt = blk_cnt(c, slot);
+    const uint32_t pw = ev.pair_word(lo, hi);
     for (int k = lane; k < c.Kpad; k += WAVE) {
         uint32_t n = k < c.K ? cnt_of(k) : 0u;
         if (n > 65535u) c.g->error = E_COUNT_OVERFLOW;
         cnt[k] = (uint16_t)n;
-        ev.fold(best, ev.candidate(n, (uint32_t)k, ov, dl));
+        ev.fold(best, ev.candidate(n, (uint32_t)k, ov, dl, pw));
     }
     best = wave_max_u64(best);
     if (lane == 0) {
@@ -724,8 +743,8 @@ __device__ bool table_insert(const BlockEval<SEEDED, WEIGHTED> &ev, uint32_t lo,
 
 // one lane: publish the re-evaluated best key of a block (or delete the block when no count >= 2 is left)
 // `best`: the block's best candidate word, 0 = nothing selectable
-template <bool SEEDED, bool WEIGHTED>
-__device__ __forceinline__ void block_commit(const BlockEval<SEEDED, WEIGHTED> &ev, int slot, unsigned long long key, const BlkHdr &h, unsigned long long best, int alive, bool tally = true) {
+template <bool SEEDED, bool WEIGHTED, bool SLACK>
+__device__ __forceinline__ void block_commit(const BlockEval<SEEDED, WEIGHTED, SLACK> &ev, int slot, unsigned long long key, const BlkHdr &h, unsigned long long best, int alive, bool tally = true) {
     const Ctx &c = ev.c;
     const uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32);
     const unsigned long long w_old = ev.word(lo, hi, h.rank, h.idx);  // bound word of the block's best entry as its header holds it
@@ -745,20 +764,21 @@ __device__ __forceinline__ void block_commit(const BlockEval<SEEDED, WEIGHTED> &
 }
 
 // Re-evaluate a block after its counts changed (new_cnt(k, old) -> new count); deletes it when no count >= 2 is left and returns true then (wave-uniform).
-template <bool SEEDED, bool WEIGHTED, class CntFn>
-__device__ bool table_update(const BlockEval<SEEDED, WEIGHTED> &ev, int slot, unsigned long long key, CntFn new_cnt, bool tally = true) {
+template <bool SEEDED, bool WEIGHTED, bool SLACK, class CntFn>
+__device__ bool table_update(const BlockEval<SEEDED, WEIGHTED, SLACK> &ev, int slot, unsigned long long key, CntFn new_cnt, bool tally = true) {
     const Ctx &c = ev.c;
     int lane = lane_id();
     const BlkHdr h = load_hdr(c, slot);
     DA_GLOBAL uint16_t *cnt = blk_cnt(c, slot);
     unsigned long long best = 0;
     int alive = 0;
+    const uint32_t pw = ev.pair_word((uint32_t)key, (uint32_t)(key >> 32));
     for (int k = lane; k < c.K; k += WAVE) {
         uint32_t old = cnt[k];
         uint32_t n = new_cnt(k, old);
         if (n != old) cnt[k] = (uint16_t)n;
         alive |= n >= 2;
-        ev.fold(best, ev.candidate(n, (uint32_t)k, h.ov, h.dl));
+        ev.fold(best, ev.candidate(n, (uint32_t)k, h.ov, h.dl, pw));
     }
     best = wave_max_u64(best);
     alive = __any(alive);
@@ -793,8 +813,8 @@ __device__ __forceinline__ SpecialPair special_pair(int row, uint32_t A, uint32_
 }
 // One wave: the block of such a pair is replaced by its exact counts `cnt` -- re-counted where it exists (deleted when no count >= 2 is left),
 // created where it does not and a count reaches 2.  ra / rb: records of rows lo / hi.  Either way the block's best entry is passed to fold_entry.
-template <bool SEEDED, bool WEIGHTED, class CntPtr>
-__device__ __forceinline__ void replace_block(const BlockEval<SEEDED, WEIGHTED> &ev, const SpecialPair &p, const RowInfo &ra, const RowInfo &rb, CntPtr cnt) {
+template <bool SEEDED, bool WEIGHTED, bool SLACK, class CntPtr>
+__device__ __forceinline__ void replace_block(const BlockEval<SEEDED, WEIGHTED, SLACK> &ev, const SpecialPair &p, const RowInfo &ra, const RowInfo &rb, CntPtr cnt) {
     const unsigned long long key = pack_pair(p.lo, p.hi);
     const int slot = p.existed ? table_find(ev.c, key, hash_pair(p.lo, p.hi)) : -1;
     if (slot >= 0)
@@ -957,7 +977,7 @@ __device__ __forceinline__ void pair_of_index(long long p, uint32_t &lo, uint32_
 
 // ------------------------------------------------------------------------------------------------ k_init_pairs
 // grid (ceil(n_pairs / 4), n_chains): one wave per initial row pair (i0 <= i1).
-template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __global__ void __launch_bounds__(256) k_init_pairs(ChainDev *chains) {
+template <class Cell, bool SEEDED = false, bool WEIGHTED = false, bool SLACK = false> __global__ void __launch_bounds__(256) k_init_pairs(ChainDev *chains) {
     ChainDev *g = &chains[blockIdx.y];
     if (g->method == M_DUMMY) return;
     const Ctx c = make_ctx<SEEDED>(g, 0);
@@ -976,7 +996,7 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __global__ voi
         if (lane_id() == 0) g->unknown_hit = 1;
         return;
     }
-    table_insert(BlockEval<SEEDED, WEIGHTED>{c, WEIGHTED ? f2u(g->dc_weight) : 0u, SEEDED ? g->tie_order : 0u}, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; });
+    table_insert(BlockEval<SEEDED, WEIGHTED, SLACK>{c, WEIGHTED ? f2u(g->dc_weight) : 0u, SEEDED ? g->tie_order : 0u, SLACK ? g->slack : 0u}, lo, hi, load_row(c.rows, lo), load_row(c.rows, hi), [&](int k) { return cnt[k]; });
 }
 
 // ================================================================================= k_iter_select2: the next pick, one step ahead
@@ -2020,9 +2040,10 @@ template <class Cell> struct UpdStep {
     const DA_GLOBAL unsigned long long *plist;
     uint32_t dcw;  // the bits of the chain's latency-penalty weight in the WEIGHTED instantiations, unused (0) in the others
     uint32_t ord;  // the chain's seeded tie order (TIE_ORDER_*) in the SEEDED instantiations, unused (0) in the others
+    uint32_t slk;  // the chain's score slack in the SLACK instantiations, unused (0) in the others
 };
 // ONE round trip: every descriptor field an update worker needs, pinned before the first branch (pin_sgpr)
-template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __forceinline__ UpdStep<Cell> load_upd_step(ChainDev *gq) {
+template <class Cell, bool SEEDED = false, bool WEIGHTED = false, bool SLACK = false> __device__ __forceinline__ UpdStep<Cell> load_upd_step(ChainDev *gq) {
     using Entry = typename RowFmt<Cell>::Entry;
     UpdStep<Cell> u;
     int iter = gq->iter;
@@ -2038,6 +2059,10 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __f
         u.ord = gq->tie_order;
     else
         u.ord = 0;
+    if constexpr (SLACK)
+        u.slk = gq->slack;
+    else
+        u.slk = 0;
     // the step being applied is iter - 1 (the selection has counted it): its search left the best entry the step does not touch in
     // spec[(iter - 1) & 1]; the best entry of every block this launch writes that reaches it goes to c_list[(iter - 1) & 1] (fold_entry)
     u.c.rword = gq->spec[(iter - 1) & 1].word;
@@ -2053,6 +2078,7 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __f
     pin_sgpr(u.c.rword, u.c.cn, u.c.cl);
     if constexpr (SEEDED) pin_sgpr(u.c.seed, u.ord);
     if constexpr (WEIGHTED) pin_sgpr(u.dcw);
+    if constexpr (SLACK) pin_sgpr(u.slk);
     u.c.tomb = KEY_TOMB - (unsigned long long)((2 * iter - 1) & 3);
     ctx_finish(u.c);
     return u;
@@ -2112,14 +2138,14 @@ __device__ __forceinline__ uint32_t block_loss(const uint32_t *cN, int k, bool r
 // partner, `rnew` the record of the new row.
 // STATS: tally the blocks found / created / deleted (benchmark instrumentation and the "peak pair blocks" statistic, DA4ML_HIP_STATS=1); the ballots, population
 // counts and the scalar registers of the three counters are 1.8 % of the batch's step (measured: 27.9 -> 27.5 us, one chain 19.5 -> 19.0), so the product runs without them
-template <class Cell, bool STATS, bool SEEDED = false, bool WEIGHTED = false>
+template <class Cell, bool STATS, bool SEEDED = false, bool WEIGHTED = false, bool SLACK = false>
 __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell> &u, const UpdLds<Cell> &s, int first, int stride, int limit, unsigned long long ref_next,
                                                 const RowInfo &rnew, unsigned int &found, unsigned int &inserts, unsigned int &deletes) {
     using F = RowFmt<Cell>;
     using Entry = typename F::Entry;
     constexpr int HW = ((sizeof(Cell) == 4 ? 24 : 60) + HL - 1) / HL;  // count words per lane (a block's words over its HL lanes): narrow layout Kpad / 2 <= 24 words, wide <= 60
     const Ctx &c = u.c;
-    const BlockEval<SEEDED, WEIGHTED> ev{c, u.dcw, u.ord};
+    const BlockEval<SEEDED, WEIGHTED, SLACK> ev{c, u.dcw, u.ord, u.slk};
     const uint32_t A = u.A, B = u.B, Nw = u.Nw;
     const int m = u.m, n_in = u.n_in, pk_shift = u.shift, pk_sub = u.sub;
     const DA_GLOBAL Entry *rl = u.rl;
@@ -2276,6 +2302,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
             auto lost = [&](int k) { return block_loss(cN, k, half != 0, rowX < pr, same, K, nb, pk_shift, pk_sub); };
             unsigned long long best = 0;
             int alive = 0;
+            const uint32_t pw = ev.pair_word(min(rowX, pr), max(rowX, pr));
 #pragma unroll
             for (int u = 0; u < HW; ++u) {
                 const int j = hl + u * HL;
@@ -2284,7 +2311,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const uint32_t n0 = o0 - lost(2 * j), n1 = o1 - lost(2 * j + 1);
                     if (n0 != o0 || n1 != o1) reinterpret_cast<DA_GLOBAL uint32_t *>(blk_ptr(c, sX) + 16)[j] = (n0 & 0xFFFFu) | (n1 << 16);
                     alive |= (n0 >= 2u) | (n1 >= 2u);
-                    const unsigned long long c0 = ev.candidate(n0, (uint32_t)(2 * j), ov, dl), c1 = ev.candidate(n1, (uint32_t)(2 * j + 1), ov, dl);
+                    const unsigned long long c0 = ev.candidate(n0, (uint32_t)(2 * j), ov, dl, pw), c1 = ev.candidate(n1, (uint32_t)(2 * j + 1), ov, dl, pw);
                     ev.fold(best, c0);
                     ev.fold(best, c1);
                 }
@@ -2343,6 +2370,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
             const int ovn = n_overlap(rp, rnew);
             const float dln = fabsf(rp.lat - rnew.lat);
             unsigned long long bestn = 0;
+            const uint32_t pwn = ev.pair_word(pr, Nw);  // (the partner is older than the new row)
             constexpr int CWN = ((sizeof(Cell) == 4 ? 24 : 60) + QG - 1) / QG;  // count words per lane
 #pragma unroll
             for (int u = 0; u < CWN; ++u) {
@@ -2351,7 +2379,7 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
                     const uint32_t n0 = cN[2 * j], n1 = cN[2 * j + 1];  // (zero beyond K: nothing ever counts there)
                     if ((n0 | n1) > 65535u) c.g->error = E_COUNT_OVERFLOW;
                     reinterpret_cast<DA_GLOBAL uint32_t *>(blk_ptr(c, nslot) + 16)[j] = (n0 & 0xFFFFu) | (n1 << 16);
-                    const unsigned long long c0 = ev.candidate(n0, (uint32_t)(2 * j), ovn, dln), c1 = ev.candidate(n1, (uint32_t)(2 * j + 1), ovn, dln);
+                    const unsigned long long c0 = ev.candidate(n0, (uint32_t)(2 * j), ovn, dln, pwn), c1 = ev.candidate(n1, (uint32_t)(2 * j + 1), ovn, dln, pwn);
                     ev.fold(bestn, c0);
                     ev.fold(bestn, c1);
                 }
@@ -2409,10 +2437,10 @@ __device__ __forceinline__ void update_partners(ChainDev *g, const UpdStep<Cell>
 // Two workgroups per chain share the work, one pair per wavefront and ONE turn each (find -> re-count / create: the longest dependent chain
 // of this kernel; with all six in one workgroup of four waves it took two turns): part 0 the four pairs with A, part 1 (B,N), (N,N) and the
 // listed entries.
-template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __forceinline__ void special_pairs(ChainDev *gq, const UpdStep<Cell> &u, int part) {
+template <class Cell, bool SEEDED = false, bool WEIGHTED = false, bool SLACK = false> __device__ __forceinline__ void special_pairs(ChainDev *gq, const UpdStep<Cell> &u, int part) {
     const Ctx &c = u.c;
     const uint32_t A = u.A, B = u.B, Nw = u.Nw;
-    const BlockEval<SEEDED, WEIGHTED> ev{c, u.dcw, u.ord};
+    const BlockEval<SEEDED, WEIGHTED, SLACK> ev{c, u.dcw, u.ord, u.slk};
     const DA_GLOBAL uint32_t *spc = (const DA_GLOBAL uint32_t *)gq->sp_cnt;
     const RowInfo ra = load_row(c.rows, A), rb = load_row(c.rows, B), rn = load_row(c.rows, Nw);
     const int lane = lane_id();
@@ -2447,17 +2475,17 @@ template <class Cell, bool SEEDED = false, bool WEIGHTED = false> __device__ __f
 
 // update_body: the partner rows [block_y * NWV * QN + ..., stride grid_y * NWV * QN) of chain `gq`'s current step, by a
 // workgroup of NWV wavefronts (k_iter_update: 256-thread blocks, grid = chains x blocks per chain).
-template <class Cell, int NWV, bool STATS, bool SEEDED = false, bool WEIGHTED = false>
+template <class Cell, int NWV, bool STATS, bool SEEDED = false, bool WEIGHTED = false, bool SLACK = false>
 __device__ __forceinline__ void update_body(ChainDev *gq, bool in_range, int block_y, int grid_y) {
     constexpr int NTHR = NWV * WAVE;
     // Grid (chains padded to a multiple of 8, blocks per chain): the chain index is the FAST grid dimension.  Workgroups go to
     // the XCDs round-robin by their linear id, so all blocks of chain c -- and block c of k_iter_select, which has the same
     // linear id modulo 8 -- run on XCD c mod 8: the table lines, bounds and lists of a chain stay in ONE of the eight
     // non-coherent L2s instead of being spread over all of them.
-    const UpdStep<Cell> u = load_upd_step<Cell, SEEDED, WEIGHTED>(gq);
+    const UpdStep<Cell> u = load_upd_step<Cell, SEEDED, WEIGHTED, SLACK>(gq);
     if (!in_range || u.done) return;
     if (block_y >= grid_y - 2) {  // the last two blocks of a chain: the six blocks of the pairs among {A, B, new row}
-        special_pairs<Cell, SEEDED, WEIGHTED>(gq, u, block_y - (grid_y - 2));
+        special_pairs<Cell, SEEDED, WEIGHTED, SLACK>(gq, u, block_y - (grid_y - 2));
         return;
     }
     grid_y -= 2;
@@ -2479,7 +2507,7 @@ __device__ __forceinline__ void update_body(ChainDev *gq, bool in_range, int blo
     copy_handoff<Cell>(u, s, tid, NTHR);  // one pass, one barrier (the column map arrives ready-made)
     __syncthreads();
     unsigned int found = 0, inserts = 0, deletes = 0;
-    update_partners<Cell, STATS, SEEDED, WEIGHTED>(gq, u, s, gw * QN, total_waves * QN, u.n_partners, ref0, rnew, found, inserts, deletes);
+    update_partners<Cell, STATS, SEEDED, WEIGHTED, SLACK>(gq, u, s, gw * QN, total_waves * QN, u.n_partners, ref0, rnew, found, inserts, deletes);
     if constexpr (!STATS) return;
     // statistics: summed per block in LDS, then ONE pair of device atomics per block.  (Four atomics per wave on one line
     // of the chain descriptor -- 640 per chain and launch, from all XCDs -- serialise at ~12 ns each and every launch had
@@ -2496,7 +2524,7 @@ __device__ __forceinline__ void update_body(ChainDev *gq, bool in_range, int blo
         if (s_stat[1] != s_stat[2]) atomicAdd(&gq->n_live, s_stat[1] - s_stat[2]);  // blocks created less blocks deleted by this workgroup (modulo 2^32)
     }
 }
-template <class Cell, bool STATS, bool SEEDED = false, bool WEIGHTED = false>
+template <class Cell, bool STATS, bool SEEDED = false, bool WEIGHTED = false, bool SLACK = false>
 __global__ void __launch_bounds__(UPD_THREADS, DA_UPD_OCC) __attribute__((amdgpu_num_sgpr(DA_UPD_SGPRS))) k_iter_update(ChainDev *chains, int n_chains) {
     // Grid (chains padded to a multiple of 8, blocks per chain): the chain index is the FAST grid dimension (see update_body)
 #ifdef DA_STEP_CLOCKS
@@ -2505,7 +2533,7 @@ __global__ void __launch_bounds__(UPD_THREADS, DA_UPD_OCC) __attribute__((amdgpu
     const int clk_par = (gk->iter - 1) & 1;
     if (clk_on && threadIdx.x == 0) CLK_MARK(gk, clk_par, 2, true);
 #endif
-    update_body<Cell, UPD_WAVES, STATS, SEEDED, WEIGHTED>(&chains[(int)blockIdx.x < n_chains ? blockIdx.x : 0], (int)blockIdx.x < n_chains, (int)blockIdx.y, (int)gridDim.y);  // clamped: the descriptor read is unconditional
+    update_body<Cell, UPD_WAVES, STATS, SEEDED, WEIGHTED, SLACK>(&chains[(int)blockIdx.x < n_chains ? blockIdx.x : 0], (int)blockIdx.x < n_chains, (int)blockIdx.y, (int)gridDim.y);  // clamped: the descriptor read is unconditional
 #ifdef DA_STEP_CLOCKS
     __syncthreads();
     if (clk_on && threadIdx.x == 0) CLK_MARK(gk, clk_par, 3, false);

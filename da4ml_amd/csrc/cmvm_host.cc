@@ -732,7 +732,7 @@ std::vector<PipeResult> solve_batch_unique(Backend &be, const std::vector<Proble
 bool same_problem(const Problem &a, const Problem &b) {
     const SolveOptions &x = a.opt, &y = b.opt;
     if (a.n_in != b.n_in || a.n_out != b.n_out || x.hard_dc != y.hard_dc || x.decompose_dc != y.decompose_dc || x.adder_size != y.adder_size ||
-        x.carry_size != y.carry_size || x.search_all != y.search_all || x.seed != y.seed || x.tie_order != y.tie_order || x.recode != y.recode || x.recode_seed != y.recode_seed || f2u(x.dc_weight) != f2u(y.dc_weight) || x.method0 != y.method0 || x.method1 != y.method1 ||
+        x.carry_size != y.carry_size || x.search_all != y.search_all || x.seed != y.seed || x.tie_order != y.tie_order || x.recode != y.recode || x.recode_seed != y.recode_seed || x.slack != y.slack || f2u(x.dc_weight) != f2u(y.dc_weight) || x.method0 != y.method0 || x.method1 != y.method1 ||
         x.qints.size() != y.qints.size() || x.lats.size() != y.lats.size())
         return false;
     // bitwise comparisons: anything that is not literally the same input is simply solved again
@@ -773,7 +773,7 @@ uint64_t problem_hash(const Problem &p) {
     mix(p.kernel, sizeof(float) * (size_t)p.n_in * p.n_out);
     if (!p.opt.qints.empty()) mix(p.opt.qints.data(), sizeof(QInt) * p.opt.qints.size());
     if (!p.opt.lats.empty()) mix(p.opt.lats.data(), sizeof(float) * p.opt.lats.size());
-    const uint32_t seed_words[6] = {(uint32_t)p.opt.seed, (uint32_t)(p.opt.seed >> 32), p.opt.tie_order, p.opt.recode, (uint32_t)p.opt.recode_seed, (uint32_t)(p.opt.recode_seed >> 32)};
+    const uint32_t seed_words[7] = {(uint32_t)p.opt.seed, (uint32_t)(p.opt.seed >> 32), p.opt.tie_order, p.opt.recode, (uint32_t)p.opt.recode_seed, (uint32_t)(p.opt.recode_seed >> 32), p.opt.slack};
     mix(seed_words, sizeof seed_words);  // (the restarts of one matrix differ in nothing else)
     const uint32_t weight_bits = f2u(p.opt.dc_weight);
     mix(&weight_bits, sizeof weight_bits);  // (nor do the points of a weight sweep)
@@ -931,10 +931,10 @@ std::vector<PipeResult> solve_batch_unique(Backend &be, const std::vector<Proble
                     continue;
             }
             if (c.phase == Candidate::NEED_STAGE0) {
-                jobs.push_back(ChainJob{c.m0.data(), p.n_in, p.n_out, parse_method(c.method0), s.qints.data(), s.lats.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed, p.opt.dc_weight, p.opt.tie_order, p.opt.recode, p.opt.recode_seed});
+                jobs.push_back(ChainJob{c.m0.data(), p.n_in, p.n_out, parse_method(c.method0), s.qints.data(), s.lats.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed, p.opt.dc_weight, p.opt.tie_order, p.opt.recode, p.opt.recode_seed, p.opt.slack});
                 owners.push_back(Pending{(int)ci, 1, c.problem});
             } else if (c.phase == Candidate::NEED_STAGE1) {
-                jobs.push_back(ChainJob{c.m1.data(), p.n_out, p.n_out, parse_method(c.method1), c.q_mid.data(), c.lat_mid.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed, p.opt.dc_weight, p.opt.tie_order, p.opt.recode, p.opt.recode_seed});
+                jobs.push_back(ChainJob{c.m1.data(), p.n_out, p.n_out, parse_method(c.method1), c.q_mid.data(), c.lat_mid.data(), p.opt.adder_size, p.opt.carry_size, p.opt.seed, p.opt.dc_weight, p.opt.tie_order, p.opt.recode, p.opt.recode_seed, p.opt.slack});
                 owners.push_back(Pending{(int)ci, 2, c.problem});
             }
         }

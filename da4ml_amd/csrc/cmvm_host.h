@@ -57,6 +57,7 @@ struct ChainJob {
     uint32_t tie_order = TIE_ORDER_RANDOM;  // which seeded order a chain with tie_seed != 0 runs (TIE_ORDER_*, cmvm_core.h); means nothing with tie_seed == 0
     uint32_t recode = RECODE_CSD;  // the signed-digit form the chain starts from (RECODE_*, digit_masks of cmvm_core.h); column-sharded chains take RECODE_CSD only
     uint64_t recode_seed = 0;  // the coin of RECODE_SEEDED; 0 under the other modes
+    uint32_t slack = 0;  // score slack (entry_rank_slack, cmvm_core.h), 0 .. 255; read with tie_seed != 0 only, which keys it; column-sharded chains take 0 only
 };
 struct ChainOut {
     int error = E_OK;
@@ -100,6 +101,8 @@ struct SolveOptions {
     uint32_t recode = RECODE_CSD;  // digit recoding of every chain of the problem (RECODE_*): both stages, every decompose_dc candidate, every latency retry, and the
                                    // adder trees the minimal latency is taken from.  The stage-1 distances count digits, which no mode changes: Stage1 stays shared
     uint64_t recode_seed = 0;  // coin of RECODE_SEEDED; normalised to 0 under CSD and COMPACT, which do not read it: one problem to the de-duplication
+    uint32_t slack = 0;  // score slack of every greedy chain of the problem (entry_rank_slack, cmvm_core.h), 0 .. 255, keyed by `seed` (a slack wants seed != 0): both stages,
+                         // every decompose_dc candidate, every latency retry.  The stage-1 distances read no score: Stage1 stays shared
 };
 
 int parse_method(const std::string &name);  // da::Method or -1

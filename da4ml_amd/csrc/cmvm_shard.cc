@@ -14,6 +14,7 @@ void ShardedBackend::run_chains(const ChainJob *jobs, ChainOut *outs, int n) {
         const bool shardable = (comm_.world > 1 || force_single) && j.n_out >= comm_.world && j.method >= 0 && j.method != M_DUMMY;
         // the same answer on every rank, before any exchange: the job is the same everywhere
         if (shardable && j.recode != RECODE_CSD) throw std::invalid_argument("column-sharded chains start from the CSD digits: no other recoding");
+        if (shardable && j.slack != 0) throw std::invalid_argument("column-sharded chains score as the reference does: no slack");
         if (shardable)
             run_one(j, outs[i]);
         else

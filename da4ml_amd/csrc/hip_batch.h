@@ -29,17 +29,22 @@ struct HipBackend::Impl::Batch {
     std::vector<Geometry> geo;
     std::vector<size_t> a_off;  // of every chain in the arena
     size_t arena_bytes = 0, budget = 0, free_b = 0;
-    std::vector<int> order;  // descriptor s of the device is chain order[s] of the call: chains with their method's own penalty weight first, of those the chains of the reference's tie order first, of those the narrow ones first, and of a width those of the regular selection carve first
+    std::vector<int> order;  // descriptor s of the device is chain order[s] of the call: chains with their method's own penalty weight first, of those the chains of the reference's tie order first, of those the narrow ones first, and of a width those of the regular selection carve first; the chains with a score slack come last
     std::vector<char> manycol;  // per chain: it runs the many-column instantiation of k_iter_select2 (sel2_manycol)
-    static constexpr int N_VAR = 16;  // kernel variants of a batch: 8 * weighted + 4 * seeded + 2 * wide + manycol (a batch of restarts mixes tie orders: restart 0 has the reference's;
-                                      // a sweep of penalty weights mixes weighted chains with those on their method's constant.  The selection kernel forms no rank: it has no weighted form)
-    int variant(int i) const { return 8 * (int)chain_weighted(jobs[i]) + 4 * (int)(jobs[i].tie_seed != 0) + 2 * (int)geo[i].wide + (int)manycol[i]; }
+    static constexpr int N_VAR = 20;  // kernel variants of a batch: 8 * weighted + 4 * seeded + 2 * wide + manycol (a batch of restarts mixes tie orders: restart 0 has the reference's;
+                                      // a sweep of penalty weights mixes weighted chains with those on their method's constant.  The selection kernel forms no rank: it has no weighted form),
+                                      // and from 16 on the chains with a score slack: 16 + 2 * wide + manycol (they have a seed and read their weight from the descriptor, whatever it is)
+    int variant(int i) const {
+        if (chain_slack(jobs[i])) return 16 + 2 * (int)geo[i].wide + (int)manycol[i];
+        return 8 * (int)chain_weighted(jobs[i]) + 4 * (int)(jobs[i].tie_seed != 0) + 2 * (int)geo[i].wide + (int)manycol[i];
+    }
+    static constexpr int sel_variant(int v) { return v < 16 ? v & 7 : 4 + (v & 3); }  // the selection kernel's instantiation: width, carve and seededness only
     struct Range {
         int first, count;
-        bool wide, manycol, seeded, weighted;
+        bool wide, manycol, seeded, weighted, slack;
     } ranges[N_VAR];
     size_t sel_lds[N_VAR] = {}, upd_lds[N_VAR] = {};  // per variant: dynamic LDS of the loop's kernels, k_iter_update blocks per chain
-    int upd_blocks[N_VAR] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+    int upd_blocks[N_VAR] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
     EventGuard events;  // declared before anything greedy_loop declares: destroyed after its streams have been drained, and after extract has read the clocks
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> sample_ev;  // three per sampled iteration
@@ -140,7 +145,7 @@ struct HipBackend::Impl::Batch {
         }
         int n_of[N_VAR] = {};
         for (int i = 0; i < n; ++i) ++n_of[variant(i)];
-        for (int v = 0, first = 0; v < N_VAR; first += n_of[v], ++v) ranges[v] = Range{first, n_of[v], (v & 2) != 0, (v & 1) != 0, (v & 4) != 0, (v & 8) != 0};
+        for (int v = 0, first = 0; v < N_VAR; first += n_of[v], ++v) ranges[v] = Range{first, n_of[v], (v & 2) != 0, (v & 1) != 0, v >= 16 || (v & 4) != 0, v >= 16 || (v & 8) != 0, v >= 16};
 
         size_t pair_lds[N_VAR] = {};
         long long max_pairs[N_VAR] = {};
@@ -164,16 +169,21 @@ struct HipBackend::Impl::Batch {
             const dim3 colgrid((max_n_out + 3) / 4, r.count), pairgrid((unsigned)((max_pairs[w] + 3) / 4), r.count);
             with_cell(r.wide, [&](auto c) {
                 hipLaunchKernelGGL(k_init_cells<decltype(c)>, colgrid, dim3(256), 0, st, base, d_recode ? d_recode + r.first : nullptr);
-                with_flag(r.seeded, [&](auto sd) {
-                    with_flag(r.weighted, [&](auto wt) { hipLaunchKernelGGL((k_init_pairs<decltype(c), decltype(sd)::value, decltype(wt)::value>), pairgrid, dim3(256), pair_lds[w], st, base); });
+                with_rank_flags(r.seeded, r.weighted, r.slack, [&](auto sd, auto wt, auto sl) {
+                    hipLaunchKernelGGL((k_init_pairs<decltype(c), decltype(sd)::value, decltype(wt)::value, decltype(sl)::value>), pairgrid, dim3(256), pair_lds[w], st, base);
                 });
             });
             HIP_CHECK(hipGetLastError());
         }
-        // one limit per instantiation of the selection kernel: it has no weighted form, so the ranges w and w + 8 launch the same function and the
-        // limit must cover the larger of the two (set once per range, the second would lower what the first had just been given)
-        for (int w = 0; w < N_VAR / 2; ++w)
-            if (ranges[w].count || ranges[w + 8].count) sel2_allow_lds<false>(ranges[w].wide, std::max(sel_lds[w], sel_lds[w + 8]), ranges[w].manycol, ranges[w].seeded);
+        // one limit per instantiation of the selection kernel: it has no weighted and no slack form, so several ranges launch the same function and
+        // the limit must cover the largest of them (set once per instantiation, a second call would lower what the first had just been given)
+        for (int sv = 0; sv < 8; ++sv) {
+            size_t most = 0;
+            bool used = false;
+            for (int w = 0; w < N_VAR; ++w)
+                if (sel_variant(w) == sv && ranges[w].count) used = true, most = std::max(most, sel_lds[w]);
+            if (used) sel2_allow_lds<false>((sv & 2) != 0, most, (sv & 1) != 0, (sv & 4) != 0);
+        }
         for (int wide = 0; wide < 2; ++wide) {  // (one limit for all instantiations of a width)
             size_t most = 0;
             for (int w = 0; w < N_VAR; ++w)
@@ -230,7 +240,11 @@ struct HipBackend::Impl::Batch {
                 if (se) HIP_CHECK(hipEventRecord(se[1], gr.stream));
                 with_flag(with_stats, [&](auto s) {
                     with_flag(ranges[gr.w].weighted, [&](auto wt) {
-                        hipLaunchKernelGGL((k_iter_update<Cell, decltype(s)::value, SEEDED, decltype(wt)::value>), upd_grid, dim3(UPD_THREADS), upd_lds[gr.w], gr.stream, base, gr.count);
+                        constexpr bool WEIGHTED = decltype(wt)::value;
+                        with_flag(SEEDED && WEIGHTED && ranges[gr.w].slack, [&](auto sl) {
+                            constexpr bool SLACK = SEEDED && WEIGHTED && decltype(sl)::value;  // (the slack kernels exist with a seed and a carried weight only)
+                            hipLaunchKernelGGL((k_iter_update<Cell, decltype(s)::value, SEEDED, WEIGHTED, SLACK>), upd_grid, dim3(UPD_THREADS), upd_lds[gr.w], gr.stream, base, gr.count);
+                        });
                     });
                 });
                 if (se) HIP_CHECK(hipEventRecord(se[2], gr.stream));

@@ -111,6 +111,18 @@ bool chain_weighted(const ChainJob &j) {
     return dc && f2u(chain_dc_weight(j)) != f2u(dc_weight_default(j.method));
 }
 
+// A chain scores with a slack (entry_rank_slack, cmvm_core.h) -- it runs the SLACK instantiations of k_init_pairs and k_iter_update -- when the job
+// sets one and has the seed that keys it (the C entry refuses a slack without a seed; a job without greedy loop reads neither)
+bool chain_slack(const ChainJob &j) { return j.slack != 0 && j.tie_seed != 0; }
+// f(std::bool_constant<SEEDED>{}, std::bool_constant<WEIGHTED>{}, std::bool_constant<SLACK>{}) for the rank-forming kernels: the slack instantiations
+// exist with a seed and a carried weight only
+template <class F> void with_rank_flags(bool seeded, bool weighted, bool slack, F &&f) {
+    if (slack)
+        f(std::true_type{}, std::true_type{}, std::true_type{});
+    else
+        with_flag(seeded, [&](auto sd) { with_flag(weighted, [&](auto wt) { f(sd, wt, std::false_type{}); }); });
+}
+
 // The job fields of a descriptor, all else zero: the chain holds the `n_loc` columns from `col0` on of the job's matrix, whose inputs are at `io`
 void fill_job(ChainDev &d, const ChainJob &j, int n_loc, int col0, unsigned char *io, const InputLayout &L) {
     std::memset(&d, 0, sizeof d);
@@ -122,6 +134,7 @@ void fill_job(ChainDev &d, const ChainJob &j, int n_loc, int col0, unsigned char
     d.tie_seed = j.tie_seed;
     d.tie_order = j.tie_seed ? j.tie_order : TIE_ORDER_RANDOM;
     d.dc_weight = chain_dc_weight(j);
+    d.slack = chain_slack(j) ? j.slack : 0u;
     d.adder_size = j.adder_size;
     d.carry_size = j.carry_size;
     d.kernel = reinterpret_cast<const float *>(io + L.kernel);
@@ -186,6 +199,8 @@ void upd_allow_lds(int device, bool wide, size_t bytes) {
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_update<decltype(c), true, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     });
 }
 // words of the optional LDS area in which the substitution block combines the row bitmaps of a young chain: dropped (0: every wave ORs its words

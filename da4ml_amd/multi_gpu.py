@@ -300,7 +300,7 @@ def solve_candidates_sharded(kernel, method0: str = 'wmc', method1: str = 'auto'
     return box[0]
 
 
-def solve_restarts_sharded(kernel, n_restarts: int, seed: int = 0, solver=None, order: str = 'random', recode: str = 'csd', **opts):
+def solve_restarts_sharded(kernel, n_restarts: int, seed: int = 0, solver=None, order: str = 'random', recode: str = 'csd', slack: int = 0, **opts):
     """``da4ml_amd.cmvm.solve_restarts`` with the restarts sharded over the ranks: restart ``r`` (tie seed
     ``cmvm.restart_seeds(n_restarts, seed)[r]``) runs on rank ``r % world``, each rank's restarts in one call on its own GPU.
     The shape of ``solve_candidates_sharded``: one all-reduce(MIN) over the cost vector, the first-strict-minimum rule, a
@@ -308,11 +308,12 @@ def solve_restarts_sharded(kernel, n_restarts: int, seed: int = 0, solver=None, 
     one-process ``solve_restarts``.  ``solver(kernels, seeds=..., **opts)`` defaults to the HIP path (``_binary.solve_many``);
     the CPU tests inject a stand-in.  ``order``: ``'random'`` or ``'newest'`` as for ``solve_restarts``; another order than the default reaches
     the solver as ``tie_order=``.  ``recode``: ``'csd'``, ``'compact'`` or ``'seeded'`` as for ``solve_restarts``; another recoding than the
-    default reaches the solver as ``recode=``."""
+    default reaches the solver as ``recode=``.  ``slack``: an int 0 .. 255 as for ``solve_restarts``; a slack other than 0 reaches the solver
+    as ``slack=``."""
     import torch
     import torch.distributed as dist
 
-    from ._binary import recode_code, tie_order_code
+    from ._binary import recode_code, slack_value, tie_order_code
     from .cmvm import first_strict_minimum, restart_seeds
 
     tie_order_code(order)
@@ -321,6 +322,8 @@ def solve_restarts_sharded(kernel, n_restarts: int, seed: int = 0, solver=None, 
     recode_code(recode)
     if recode != 'csd':
         opts = {**opts, 'recode': recode}
+    if slack_value(slack):
+        opts = {**opts, 'slack': int(slack)}
 
     rank, world, local, device = init()
     if solver is None:

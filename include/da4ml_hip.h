@@ -161,6 +161,26 @@ int da_solve_batch_recode(int count, const float *const *kernels, const int64_t 
                           const da_recode_opts *recode /* [count] or NULL */, const float *const *qintervals, const float *const *latencies,
                           da_result **results);
 
+/* da_solve_batch_recode with a score slack per problem (addition, no reference counterpart).  The greedy search takes the best-scored pair
+ * at every step; a chain with a slack draws its pick from the pairs whose score lies within a small fraction of the best -- the restricted
+ * candidate list of a randomised greedy search.  Every table entry gets a discount of at most slack / 256 of its score, a keyed hash of
+ * (row pair, key, seed): with byte = slack_byte(id0, id1, key index, seed) in 0 .. 255 and base = count (mc family) or count * overlap (wmc
+ * family), base becomes base - ((base * ((byte * slack) >> 8)) >> 8) when 0 < base < 2^24; the latency penalty, the cut of the -dc methods
+ * and the tie order are what they were (entry_rank_slack, cmvm_core.h).  The slack goes into every greedy chain of the problem: both stages,
+ * every decompose_dc candidate, every latency retry.  da_solve_opts and da_recode_opts cannot grow (their sizes are pinned), hence the third array.
+ * Contract: search == NULL, or slack 0, is da_solve_batch_recode bit for bit; slack > 255, or a struct_size other than
+ * sizeof(da_search_opts), gives DA_ERR_VALUE; slack != 0 with seed == 0 in the problem's da_solve_opts gives DA_ERR_VALUE (the seed keys the
+ * discounts); the result of a problem depends on nothing but its own matrix and options, whatever else the batch holds and wherever it stands
+ * in it; the same inputs give the same result on every run.  A restart dimension (da4ml_amd.cmvm.solve_restarts(..., slack=)), never a
+ * default: a single slack chain is as often dearer than the reference's graph as cheaper.  Column-sharded chains take no slack. */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t slack; /* 0 .. 255; 0: none */
+} da_search_opts;
+int da_solve_batch_search(int count, const float *const *kernels, const int64_t *n_in, const int64_t *n_out, const da_solve_opts *opts /* [count] */,
+                          const da_recode_opts *recode /* [count] or NULL */, const da_search_opts *search /* [count] or NULL */,
+                          const float *const *qintervals, const float *const *latencies, da_result **results);
+
 /* ---- column-sharded solve (BASELINE config C4; addition, no reference counterpart) ------------------------------------------
  * da_solve with every greedy chain sharded over the output COLUMNS of its matrix across `world` processes (one per GPU):
  * rank g holds the digits of columns [g n_out / world, (g+1) n_out / world), the pair-count table is replicated, and per
